@@ -4,7 +4,9 @@
 Mirrors the reference's ``thunder/benchmarks/benchmark_litgpt.py`` headline run
 (``docs/source/intermediate/benchmarking.rst:36-54``: 10,690 tokens/s/GPU on 1×H100).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3          # headline only: set up, warm up, time, print
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full   # + the PyTorch eager baseline (speedup_vs_eager)
+    python bench.py --steps 10 --warmup 3 --dump-outputs DIR  # + the last step's outputs as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
 
 Synthetic token ids and random-init weights of the exact Llama-2-7B architecture
@@ -63,10 +65,19 @@ def parse_args():
     p.add_argument("--checkpoint-activations", action="store_true",
                    help="recompute every transformer block in the backward (memory for longer sequences)")
     p.add_argument("--n-layer", type=int, default=None, help="override layer count (debug only; invalid for the headline)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline run also measure everything that takes runs of its own (today: the "
+                        "PyTorch eager baseline of --eager-baseline auto).  Off by default: a plain run sets up, "
+                        "warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32): "
+                        "loss.npy (the step's return value), loss_curve.npy (every step's loss, warmup first) and "
+                        "params_sample.npy (a fixed, seeded sample of every updated parameter).  Inputs are seeded, "
+                        "so two builds can be compared output for output")
     p.add_argument("--eager-baseline", default="auto", choices=["auto", "on", "off"],
                    help="also time PyTorch eager on the same config for speedup_vs_eager (auto: on for the 1-GPU "
-                        "thunder run; --eager-warmup + --eager-steps from the same init and data, outside "
-                        "thunder's timed region; both per-step loss curves go into the JSON line)")
+                        "thunder run under --full; --eager-warmup + --eager-steps from the same init and data, "
+                        "outside thunder's timed region; both per-step loss curves go into the JSON line)")
     p.add_argument("--eager-steps", type=int, default=None, help="default: --steps (same loss-curve length)")
     p.add_argument("--eager-warmup", type=int, default=None, help="default: --warmup")
     p.add_argument("--lr", type=float, default=1e-4,
@@ -124,7 +135,35 @@ def _force_dist() -> bool:
     return os.environ.get("LTA_BENCH_FORCE_DIST") == "1"
 
 
-def run(args, rank, world, device, mode, steps=None, warmup=None):
+DUMP_SAMPLE_SEED = 4321
+DUMP_SAMPLE_PER_PARAM = 8192
+DUMP_MAX_BYTES = 48 << 20  # well under the 64 MB a dump may take
+
+
+def dump_outputs(dump_dir, rank, loss, losses, params):
+    """What the last timed step handed back: its loss, the losses of all steps, and a fixed seeded
+    sample of every parameter the step updated (the whole of Llama-2-7B would be 27 GB in float32)."""
+    import numpy as np
+
+    os.makedirs(dump_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    np.save(os.path.join(dump_dir, f"loss{sfx}.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(dump_dir, f"loss_curve{sfx}.npy"),
+            torch.stack([l.float().reshape(()) for l in losses]).cpu().numpy())
+    k = max(1, min(DUMP_SAMPLE_PER_PARAM, DUMP_MAX_BYTES // 4 // max(1, len(params))))
+    g = torch.Generator()  # CPU: the same indices on every build and device
+    g.manual_seed(DUMP_SAMPLE_SEED)
+    sample = []
+    for p in params:
+        flat = p.detach().reshape(-1)
+        if flat.numel() == 0:
+            continue
+        idx = torch.randint(0, flat.numel(), (min(k, flat.numel()),), generator=g)
+        sample.append(flat[idx.to(flat.device)].float().cpu())
+    np.save(os.path.join(dump_dir, f"params_sample{sfx}.npy"), torch.cat(sample).numpy())
+
+
+def run(args, rank, world, device, mode, steps=None, warmup=None, dump_dir=None):
     import lightning_thunder_amd as thunder
 
     steps = args.steps if steps is None else steps
@@ -264,6 +303,8 @@ def run(args, rank, world, device, mode, steps=None, warmup=None):
 
         log(rank, f"[gemm] calls per backend since start (gemm4 = hand MFMA kernel, torch = library): "
                   f"{_g.last_gemm_backend_counts()}")
+    if dump_dir is not None:
+        dump_outputs(dump_dir, rank, loss, losses, params)
     curve = [round(v, 4) for v in torch.stack([l.float() for l in losses]).cpu().tolist()]
     del model, opt, fwd, params, losses, loss
     return dt, cfg, mem, parallel, curve
@@ -310,7 +351,7 @@ def main():
         else:
             torch.distributed.init_process_group(backend, timeout=timeout)
 
-    dt, cfg, mem, parallel, curve = run(args, rank, world, device, args.mode)
+    dt, cfg, mem, parallel, curve = run(args, rank, world, device, args.mode, dump_dir=args.dump_outputs)
     data_parallel = parallel != "tp"
     tokens = args.steps * args.mbs * args.seq * (world if data_parallel else 1)
     value = tokens / dt
@@ -319,8 +360,8 @@ def main():
 
     tflops = flops_per_token(cfg, args.seq) * per_gpu / 1e12
     speedup = eager_ms = curve_eager = None
-    want_eager = args.eager_baseline == "on" or (args.eager_baseline == "auto" and world == 1 and not _force_dist()
-                                                 and not args.lora)
+    want_eager = args.eager_baseline == "on" or (args.eager_baseline == "auto" and args.full and world == 1
+                                                 and not _force_dist() and not args.lora)
     if want_eager and args.mode == "thunder":
         # PyTorch eager on the same model / batch / optimizer semantics (torch fused AdamW), after
         # thunder's timed region; thunder's model and optimizer state are freed first

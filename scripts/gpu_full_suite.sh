@@ -6,6 +6,6 @@ export TMPDIR=/tmp
 rm -f $OUT/status.log
 run pytest_gpu 700 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 run smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
-run bench 400 python bench.py
+run bench 400 python bench.py --full
 rm -rf $OUT/prof_Gemma
 run prof_Gemma 420 rocprofv3 --kernel-trace --stats -d $OUT/prof_Gemma -o run --output-format csv -- python bench.py --model Gemma-7b --steps 3 --warmup 2 --eager-baseline off
