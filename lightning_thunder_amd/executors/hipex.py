@@ -885,6 +885,290 @@ def _group_decode_projections(trace):
     return new
 
 
+# =========================================================================================
+# MXFP4 decode GEMV (lta::mxfp4_linear with <= 8 rows) with the same prologue / epilogues / groups
+# =========================================================================================
+def _mxfp4_decode_linear_meta(x, q, s, bias=None, residual=None, act=None, gate_q=None, gate_s=None, norm=False,
+                              norm_weight=None, eps=1e-5):
+    return TensorProxy(like=x, shape=tuple(x.shape[:-1]) + (q.shape[0],))
+
+
+def _mxfp4_decode_linear_impl(x, q, s, bias=None, residual=None, act=None, gate_q=None, gate_s=None, norm=False,
+                              norm_weight=None, eps=1e-5):
+    from ..ops import mxfp4 as mx
+
+    K, N = x.shape[-1], q.shape[0]
+    x2 = x.reshape(-1, K)
+    r2 = None if residual is None else residual.reshape(-1, N)
+    kw = dict(bias=bias, residual=r2, act=act, gate_q=gate_q, gate_s=gate_s)
+    if mx.gemv_fused_supported(x2, q, s, norm_weight=norm_weight, **kw):
+        y = mx.gemv_fused(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps, **kw)
+    else:  # operands the kernel does not take (alignment, > 8 rows): the same math in torch
+        y = mx.gemv_fused_reference(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps, **kw)
+    return y.reshape(*x.shape[:-1], N)
+
+
+def _mxfp4_decode_group_meta(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
+    if packed:
+        return TensorProxy(like=x, shape=tuple(x.shape[:-1]) + (sum(q.shape[0] for q, _ in weights),))
+    return tuple(TensorProxy(like=x, shape=tuple(x.shape[:-1]) + (q.shape[0],)) for q, _ in weights)
+
+
+def _mxfp4_decode_group_impl(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
+    from ..ops import mxfp4 as mx
+
+    x2 = x.reshape(-1, x.shape[-1])
+    if all(mx.gemv_fused_supported(x2, q, s, norm_weight=norm_weight) for q, s in weights):
+        outs = mx.gemv_group(x2, list(weights), norm=norm, norm_weight=norm_weight, eps=eps, packed=packed)
+    else:
+        outs = [mx.gemv_fused_reference(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps) for q, s in weights]
+        if packed:
+            outs = torch.cat(outs, -1)
+    if packed:
+        return outs.reshape(*x.shape[:-1], outs.shape[-1])
+    return tuple(o.reshape(*x.shape[:-1], o.shape[-1]) for o in outs)
+
+
+hip_mxfp4_decode_linear = ex.register_operator("hip_mxfp4_decode_linear", meta=_mxfp4_decode_linear_meta,
+                                               fn=_mxfp4_decode_linear_impl)
+hip_mxfp4_decode_linear_group = ex.register_operator("hip_mxfp4_decode_linear_group", meta=_mxfp4_decode_group_meta,
+                                                     fn=_mxfp4_decode_group_impl)
+# The norm prologue is recomputed by every wave of the 4-bit GEMV; it pays only while the launch is
+# weight-bound (profiles/mxfp4_decode_fusion.txt: a win at 1 row, a loss from 2 rows on the 12288 x
+# 4096 qkv weight and at 8 rows on every site), so the pass folds the norm for single-row decode only.
+_MXFP4_NORM_MAX_ROWS = 1
+_MXFP4_LINEAR_IDS = ("custom_op.lta::mxfp4_linear", "custom_op.custom_op_impl_custom_op_lta_mxfp4_linear")
+
+
+def _fuse_mxfp4_decode(trace):
+    """``lta::mxfp4_linear`` on <= 8 bf16 rows (4-bit decode) -> ``hip_mxfp4_decode_linear``, with what
+    the bf16 decode GEMV carries folded into the launch:
+
+    * the SwiGLU pair ``hip_swiglu(op(x, W1), op(x, W3))`` (or ``mul(silu(a), b)``) -> one gated op;
+    * ``silu(op(...))`` -> ``act="silu"``; ``op(...) + r`` -> the residual epilogue;
+    * ``hip_rms_norm_fwd`` feeding only such ops (rstd unused) -> their norm prologue (one row only:
+      ``_MXFP4_NORM_MAX_ROWS``);
+    * two or three plain siblings of one x (attention q / k / v) -> ``hip_mxfp4_decode_linear_group``
+      (``packed`` when only a trailing ``cat(..., -1)`` reads them).
+    ``LTA_MXFP4_DECODE_FUSION=0`` leaves the custom op in place (A/B)."""
+    import os
+
+    if os.environ.get("LTA_MXFP4_DECODE_FUSION", "1") == "0":
+        return trace
+    from ..core.trace import from_trace, TraceProvenance
+
+    bsyms = list(trace.bound_symbols)
+    cand: dict[int, dict] = {}  # position -> operands of the fused op emitted there
+    for i, b in enumerate(bsyms):
+        if b.sym.id not in _MXFP4_LINEAR_IDS:
+            continue
+        p = dict(zip(("x", "q", "s", "bias", "fp4"), b.args))
+        p.update({k: v for k, v in b.kwargs.items() if k in ("bias",)})
+        x, q, s, bias = p.get("x"), p.get("q"), p.get("s"), p.get("bias")
+        if not all(isinstance(v, TensorProxy) for v in (x, q, s)) or not isinstance(b.output, TensorProxy):
+            continue
+        if x.device.type != "cuda" or x.dtype != torch.bfloat16 or _rows(x) > _GEMV_MAX_ROWS or q.ndim != 2:
+            continue
+        if any(getattr(v, "requires_grad", False) for v in (x, bias, b.output)):
+            continue  # the op's autograd stays with the custom op
+        cand[i] = dict(x=x, q=q, s=s, bias=bias, residual=None, act=None, gate_q=None, gate_s=None, norm=False,
+                       norm_weight=None, eps=1e-5, out=b.output)
+    if not cand:
+        return trace
+    drop: set[int] = set()
+    group: dict[int, tuple] = {}  # position -> (members' operands, packed output or None)
+    out_names = {o.name for o in tree_flatten(trace.output)[0] if isinstance(o, TensorProxy)} \
+        if trace.output is not None else set()
+
+    def operands(k):
+        if k in cand:
+            return [v for v in cand[k].values() if isinstance(v, TensorProxy) and v is not cand[k]["out"]]
+        return bsyms[k].flat_proxy_args
+
+    def count_uses():
+        u = {n: 1 for n in out_names}
+        for k in range(len(bsyms)):
+            if k not in drop:
+                for a in operands(k):
+                    u[a.name] = u.get(a.name, 0) + 1
+        return u
+
+    def plain(c, epilogue=True):
+        return c["gate_q"] is None and (not epilogue or (c["bias"] is None and c["residual"] is None and c["act"] is None))
+
+    producer = {c["out"].name: i for i, c in cand.items()}  # outputs of the fused ops, as they move
+    made_by = {o.name: i for i, b in enumerate(bsyms) for o in b.flat_proxy_outs}
+
+    def move(j, i, out, **changes):  # the fused op of position j is emitted at i (a consumer it absorbs)
+        c = cand.pop(j)
+        c.update(changes, out=out)
+        cand[i] = c
+        drop.add(j)
+        producer.pop(c["out"].name, None)
+        producer[out.name] = i
+
+    def gate_pair(i, a, g, out, extra=()):
+        ja, jg = producer.get(a.name), producer.get(g.name)
+        if ja is None or jg is None or ja == jg or uses.get(a.name) != 1 or uses.get(g.name) != 1:
+            return False
+        ca, cg = cand[ja], cand[jg]
+        if ca["x"].name != cg["x"].name or not plain(ca) or not plain(cg) or ca["norm"] or cg["norm"]:
+            return False
+        if tuple(ca["q"].shape) != tuple(cg["q"].shape) or out.dtype != a.dtype:
+            return False
+        cand.pop(jg)
+        producer.pop(g.name, None)
+        drop.add(jg)
+        drop.update(extra)
+        move(ja, i, out, act="silu", gate_q=cg["q"], gate_s=cg["s"])
+        return True
+
+    n_gated = n_act = n_res = n_norm = n_group = 0
+    # SwiGLU pairs: hip_swiglu(a, b), or written out as mul(silu(a), b) (HF LlamaMLP)
+    uses = count_uses()
+    for i, b in enumerate(bsyms):
+        if i in drop or i in cand or len(b.args) != 2 or not all(isinstance(a, TensorProxy) for a in b.args):
+            continue
+        if b.sym is hip_swiglu:
+            n_gated += gate_pair(i, b.args[0], b.args[1], b.output)
+        elif b.sym.name in ("mul", "torch_mul"):
+            for s_arg, g_arg in (b.args, b.args[::-1]):
+                js = made_by.get(s_arg.name)
+                if js is None or js in drop or js in cand or uses.get(s_arg.name) != 1:
+                    continue
+                sb = bsyms[js]
+                if sb.sym.name not in ("silu", "torch_silu") or not sb.args:
+                    continue
+                if len(sb.args) > 1 and sb.args[1] not in (False, None) or not isinstance(sb.args[0], TensorProxy):
+                    continue
+                if gate_pair(i, sb.args[0], g_arg, b.output, extra=(js,)):
+                    n_gated += 1
+                    break
+
+    # linear -> silu
+    uses = count_uses()
+    for i, b in enumerate(bsyms):
+        if i in drop or i in cand or b.sym.name not in ("silu", "torch_silu") or not b.args:
+            continue
+        a = b.args[0]
+        if len(b.args) > 1 and b.args[1] not in (False, None) or not isinstance(a, TensorProxy):
+            continue
+        j = producer.get(a.name)
+        if j is None or uses.get(a.name) != 1 or b.output.dtype != a.dtype:
+            continue
+        c = cand[j]
+        if c["gate_q"] is not None or c["act"] is not None or c["residual"] is not None:
+            continue
+        move(j, i, b.output, act="silu")
+        n_act += 1
+
+    # residual adds
+    uses = count_uses()
+    for i, b in enumerate(bsyms):
+        if i in drop or i in cand or b.sym.name not in ("torch_add", "add") or b.kwargs.get("alpha") not in (None, 1):
+            continue
+        if len(b.args) < 2 or not all(isinstance(a, TensorProxy) for a in b.args[:2]):
+            continue
+        for pos in (0, 1):
+            y, r = b.args[pos], b.args[1 - pos]
+            j = producer.get(y.name)
+            if j is None or uses.get(y.name) != 1 or y.name == r.name:
+                continue
+            c = cand[j]
+            if c["gate_q"] is not None or c["residual"] is not None:
+                continue
+            if tuple(r.shape) != tuple(y.shape) or r.dtype != y.dtype or tuple(b.output.shape) != tuple(y.shape):
+                continue
+            move(j, i, b.output, residual=r)  # emitted where the add was: r exists there
+            n_res += 1
+            break
+
+    # RMSNorm prologues
+    uses = count_uses()
+    for i, b in enumerate(bsyms):
+        if i in drop or b.sym is not hip_rms_norm_fwd:
+            continue
+        y, rstd = b.output
+        x, g, eps = b.args[0], b.args[1], b.args[2]
+        if uses.get(rstd.name, 0) or not isinstance(eps, (int, float)) or _rows(x) > _MXFP4_NORM_MAX_ROWS:
+            continue
+        consumers = [k for k in range(len(bsyms)) if k not in drop and any(a.name == y.name for a in operands(k))]
+        ok = bool(consumers) and len(consumers) == uses.get(y.name, 0)
+        for k in consumers:
+            c = cand.get(k)
+            ok = ok and c is not None and not c["norm"] and c["x"].name == y.name and all(
+                getattr(v, "name", None) != y.name for key, v in c.items() if key not in ("x", "out"))
+        if not ok:
+            continue
+        for k in consumers:
+            cand[k].update(x=x, norm=True, norm_weight=g, eps=float(eps))
+        drop.add(i)
+        n_norm += 1
+
+    # sibling projections of one x and norm
+    sibs: dict = {}
+    for i in sorted(cand):
+        c = cand[i]
+        if plain(c):
+            sibs.setdefault((c["x"].name, c["norm"], getattr(c["norm_weight"], "name", None), c["eps"]), []).append(i)
+    uses = count_uses()
+    for ci, cb in enumerate(bsyms):
+        if ci in drop or cb.sym.name not in ("cat", "torch_cat", "cat_prim") or not cb.args \
+                or not isinstance(cb.args[0], (list, tuple)):
+            continue
+        parts = cb.args[0]
+        dim = cb.args[1] if len(cb.args) > 1 else cb.kwargs.get("dim", 0)
+        if not 2 <= len(parts) <= 3 or not all(isinstance(p, TensorProxy) for p in parts) \
+                or dim not in (-1, parts[0].ndim - 1):
+            continue
+        js = [producer.get(p.name) for p in parts]
+        if any(j is None or uses.get(p.name) != 1 for j, p in zip(js, parts)) or len(set(js)) != len(js):
+            continue
+        key = next((k for k, idxs in sibs.items() if js[0] in idxs), None)
+        if key is None or any(j not in sibs[key] for j in js):
+            continue
+        group[ci] = ([cand.pop(j) for j in js], cb.output)
+        drop.update(js)
+        sibs[key] = [j for j in sibs[key] if j not in js]
+        n_group += 1
+    for idxs in sibs.values():
+        for c0 in range(0, len(idxs) - 1, 3):
+            chunk = idxs[c0:c0 + 3]
+            if len(chunk) < 2:
+                continue
+            group[chunk[0]] = ([cand.pop(j) for j in chunk], None)  # x and the norm weight exist there
+            drop.update(chunk[1:])
+            n_group += 1
+
+    out = []
+    for i, b in enumerate(bsyms):
+        if i in group:
+            members, packed_out = group[i]
+            c = members[0]
+            ws = tuple((m["q"], m["s"]) for m in members)
+            if packed_out is not None:
+                nb = hip_mxfp4_decode_linear_group.bind(c["x"], ws, c["norm"], c["norm_weight"], c["eps"], True,
+                                                        output=packed_out)
+            else:
+                nb = hip_mxfp4_decode_linear_group.bind(c["x"], ws, c["norm"], c["norm_weight"], c["eps"],
+                                                        output=tuple(m["out"] for m in members))
+            out.append(ex.bind_call_ctx(nb))
+        elif i in cand:
+            c = cand[i]
+            out.append(ex.bind_call_ctx(hip_mxfp4_decode_linear.bind(
+                c["x"], c["q"], c["s"], c["bias"], c["residual"], c["act"], c["gate_q"], c["gate_s"], c["norm"],
+                c["norm_weight"], c["eps"], output=c["out"])))
+        elif i not in drop:
+            out.append(b)
+    new = from_trace(trace)
+    new.bound_symbols = out
+    new.scopes = [new.bound_symbols]
+    new.set_provenance(TraceProvenance(
+        f"hipex: MXFP4 decode GEMV fusion ({n_gated} gated pair(s), {n_act} activation(s), {n_res} residual(s), "
+        f"{n_norm} norm prologue(s), {n_group} group(s))"))
+    return new
+
+
 def _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
     B, T, _ = qkv.shape
     return TensorProxy(like=qkv, shape=(B, n_head, T, head_size)), TensorProxy(like=kc), TensorProxy(like=vc)
@@ -1477,8 +1761,8 @@ def _fuse_fp8_attn_out_casts(trace):
 
 def _post_claim(trace):
     return _fuse_attn_bwd_rope(_fuse_fp8_qkv_rope_gemm(_fuse_qkv_rope_gemm(_group_decode_projections(_fuse_kv_cache_writes(_fuse_swiglu_gemms(
-        _fuse_decode_gemv(_fuse_fp8_rms_bwd_casts(_fuse_rms_bwd_residual(_fuse_linear_epilogues(
-            _fuse_fp8_attn_out_casts(_fuse_fp8_cast_producers(trace))))))))))))
+        _fuse_mxfp4_decode(_fuse_decode_gemv(_fuse_fp8_rms_bwd_casts(_fuse_rms_bwd_residual(_fuse_linear_epilogues(
+            _fuse_fp8_attn_out_casts(_fuse_fp8_cast_producers(trace)))))))))))))
 
 
 ex.post_claim_pass = _post_claim

@@ -14,13 +14,20 @@ from __future__ import annotations
 
 import torch
 
-from ._lib import require, stream_ptr, check, register_signature, c_int, c_int64, c_void_p, DTYPE_CODE
+import ctypes
+
+from ._lib import require, stream_ptr, check, register_signature, c_int, c_int64, c_float, c_void_p, DTYPE_CODE
 
 register_signature("lta_mxfp4_cast", [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
 register_signature("lta_gemm_nt_mxfp4", [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                          c_int, c_int, c_int, c_int, c_void_p])
 register_signature("lta_gemv_mxfp4", [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                       c_int, c_void_p])
+register_signature("lta_gemv_mxfp4_fused", [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float,
+                                            c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_void_p])
+register_signature("lta_gemv_mxfp4_group", [c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_int, c_int, c_void_p])
 GEMV_MAX_ROWS = 8
 
 BLOCK = 32
@@ -139,3 +146,139 @@ def gemv(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, bias: torch.Tensor |
                                    y.data_ptr(), M, N, K, x2.stride(0), y.stride(0), stream_ptr(x.device)),
           "lta_gemv_mxfp4")
     return y.reshape(*x.shape[:-1], N)
+
+
+# ---- decode GEMV with the norm prologue / gated pair / bias-activation-residual epilogue ------------
+_FUSED_ACT = {None: 0, "none": 0, "gelu_tanh": 1, "silu": 3, "relu": 4}  # codes of ops/gemm.py ACT
+
+
+def _act_reference(v: torch.Tensor, act) -> torch.Tensor:
+    if act in (None, "none"):
+        return v
+    if act == "silu":
+        return torch.nn.functional.silu(v)
+    if act == "gelu_tanh":
+        return torch.nn.functional.gelu(v, approximate="tanh")
+    if act == "relu":
+        return torch.relu(v)
+    raise ValueError(f"gemv_fused: unsupported activation {act!r}")
+
+
+def gemv_fused_reference(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, *, bias=None, residual=None, act=None,
+                         gate_q=None, gate_s=None, norm: bool = False, norm_weight=None,
+                         eps: float = 1e-5) -> torch.Tensor:
+    """Pure-torch specification of ``gemv_fused`` (and its fallback for operands the kernel does
+    not take): RMSNorm rounded to x's dtype; the product against ``dequantize(q, s)`` in fp32; with
+    a gate weight both products rounded to x's dtype and ``act(a) * b``, otherwise ``act(a + bias)
+    + residual`` in fp32; one final rounding."""
+    dt = x.dtype
+    xf = x.float()
+    if norm:
+        xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+        if norm_weight is not None:
+            xf = xf * norm_weight.float()
+        xf = xf.to(dt).float()
+    v = xf @ dequantize(q, s).T
+    if gate_q is not None:
+        if bias is not None or residual is not None:
+            raise ValueError("gemv_fused: a gated pair takes no bias or residual")
+        b = (xf @ dequantize(gate_q, gate_s).T).to(dt).float()
+        v = _act_reference(v.to(dt).float(), act) * b
+    else:
+        if bias is not None:
+            v = v + bias.float()
+        v = _act_reference(v, act)
+        if residual is not None:
+            v = v + residual.float()
+    return v.to(dt)
+
+
+def _weight_ok(q, s, K: int) -> bool:
+    return (q.dim() == 2 and q.dtype == torch.uint8 and s.dtype == torch.uint8 and q.is_cuda and s.is_cuda
+            and q.shape[1] * 2 == K and tuple(s.shape) == (q.shape[0], K // BLOCK) and q.is_contiguous()
+            and s.is_contiguous())
+
+
+def gemv_fused_supported(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, *, bias=None, residual=None, act=None,
+                         gate_q=None, gate_s=None, norm_weight=None) -> bool:
+    """Whether ``gemv_fused`` / ``gemv_group`` take these operands: x [1..8, K] bf16 on the GPU with
+    K % 32 == 0, unit element stride, a row stride that is a multiple of 8 and a 16-byte aligned
+    base; contiguous packed weights and scales; bf16 bias / residual / norm weight."""
+    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 2 or act not in _FUSED_ACT:
+        return False
+    M, K = x.shape
+    if not 1 <= M <= GEMV_MAX_ROWS or K < BLOCK or K % BLOCK or x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+        return False
+    if not _weight_ok(q, s, K):
+        return False
+    N = q.shape[0]
+    if (gate_q is None) != (gate_s is None):
+        return False
+    if gate_q is not None and (bias is not None or residual is not None or not _weight_ok(gate_q, gate_s, K)
+                               or gate_q.shape != q.shape):
+        return False
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N or not bias.is_contiguous()):
+        return False
+    if residual is not None and (residual.dtype != x.dtype or tuple(residual.shape) != (M, N)
+                                 or residual.stride(1) != 1):
+        return False
+    if norm_weight is not None and (norm_weight.dtype != x.dtype or norm_weight.numel() != K
+                                    or not norm_weight.is_contiguous() or norm_weight.data_ptr() % 16):
+        return False
+    return True
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def gemv_fused(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, *, bias=None, residual=None, act=None, gate_q=None,
+               gate_s=None, norm: bool = False, norm_weight=None, eps: float = 1e-5) -> torch.Tensor:
+    """``act(x' . dequant(q, s)^T + bias) + residual`` for x [M <= 8, K] bf16 in one launch of the
+    4-bit weight-streaming kernel (``csrc/mxfp4.hip``).  ``norm=True``: ``x' = rmsnorm(x) *
+    norm_weight``; ``gate_q`` / ``gate_s`` (same shape as q / s): ``act(x' W^T) * (x' Wg^T)``, the
+    SwiGLU up-projection pair.  Operands must satisfy ``gemv_fused_supported``."""
+    if not gemv_fused_supported(x, q, s, bias=bias, residual=residual, act=act, gate_q=gate_q, gate_s=gate_s,
+                                norm_weight=norm_weight):
+        raise ValueError(f"gemv_fused: unsupported operands x {tuple(x.shape)} {x.dtype}, q {tuple(q.shape)}")
+    M, K = x.shape
+    N = q.shape[0]
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    check(require().lta_gemv_mxfp4_fused(x.data_ptr(), q.data_ptr(), s.data_ptr(), _ptr(gate_q), _ptr(gate_s),
+                                         _ptr(norm_weight), int(norm), float(eps), _ptr(bias), _ptr(residual),
+                                         y.data_ptr(), M, N, K, x.stride(0), y.stride(0),
+                                         0 if residual is None else residual.stride(0), _FUSED_ACT[act],
+                                         stream_ptr(x.device)), "lta_gemv_mxfp4_fused")
+    return y
+
+
+def gemv_group(x: torch.Tensor, weights, *, norm: bool = False, norm_weight=None, eps: float = 1e-5,
+               packed: bool = False):
+    """``[x' . dequant(q, s)^T for (q, s) in weights]`` (<= 3 weights sharing x and the norm, e.g.
+    attention q / k / v) in ONE launch.  ``packed``: the outputs are adjacent column ranges of one
+    [M, sum N] tensor, returned alone."""
+    if not 1 <= len(weights) <= 3:
+        raise ValueError("gemv_group takes 1 to 3 weights")
+    for q, s in weights:
+        if not gemv_fused_supported(x, q, s, norm_weight=norm_weight):
+            raise ValueError(f"gemv_group: unsupported operands x {tuple(x.shape)} {x.dtype}, q {tuple(q.shape)}")
+    M, K = x.shape
+    ns = [q.shape[0] for q, _ in weights]
+    if packed:
+        buf = torch.empty((M, sum(ns)), dtype=x.dtype, device=x.device)
+        outs = list(buf.split(ns, dim=1))
+    else:
+        outs = [torch.empty((M, n), dtype=x.dtype, device=x.device) for n in ns]
+    n = len(weights)
+    pad = [None] * (3 - n)
+    qs = (ctypes.c_void_p * 3)(*[q.data_ptr() for q, _ in weights], *pad)
+    ss = (ctypes.c_void_p * 3)(*[s.data_ptr() for _, s in weights], *pad)
+    ys = (ctypes.c_void_p * 3)(*[o.data_ptr() for o in outs], *pad)
+    nn = (ctypes.c_int * 3)(*ns, *([0] * (3 - n)))
+    ldy = (ctypes.c_int * 3)(*[o.stride(0) for o in outs], *([0] * (3 - n)))
+    check(require().lta_gemv_mxfp4_group(x.data_ptr(), _ptr(norm_weight), int(norm), float(eps), n,
+                                         ctypes.cast(qs, c_void_p), ctypes.cast(ss, c_void_p),
+                                         ctypes.cast(ys, c_void_p), ctypes.cast(nn, c_void_p),
+                                         ctypes.cast(ldy, c_void_p), M, K, x.stride(0), stream_ptr(x.device)),
+          "lta_gemv_mxfp4_group")
+    return buf if packed else outs
