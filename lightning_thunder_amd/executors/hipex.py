@@ -1180,6 +1180,7 @@ def _qkv_rope_cache_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_
     if qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size):
         return qkv_rope_cache_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos)
     q, k, v = qkv_rope_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
+    pos = pos if pos.dtype == torch.int64 else pos.long()  # index_copy_ takes int64 indices only
     return q, kc.index_copy_(2, pos, k), vc.index_copy_(2, pos, v)
 
 

@@ -1004,6 +1004,12 @@ def test_decode_gemv_fusion_in_litgpt_decode():
 def test_argmax_rows_kernel(dtype, R, V):
     from lightning_thunder_amd.ops.sampling import argmax_last
 
+    # argmax_last runs the kernel only for a row stride that is a multiple of 8 elements and falls back
+    # to torch otherwise.  Of the cases here only (1, 128256) reaches it in the first call (V % 8 == 0,
+    # so without the scalar tail loop), and in the strided second call only V = 7 (row stride 5 * 8);
+    # (3, 32003), (2, 7) and the strided slices at V = 128256 / 32003 compare torch with torch.  The
+    # kernel at odd V, ties, infinities and NaN are checked (with a spy on the launch) in
+    # tests/test_decode_kernels.py.
     torch.manual_seed(0)
     x = torch.randn(R, V, device="cuda", dtype=dtype)
     x[0, V // 3] = 100.0
