@@ -136,6 +136,10 @@ __device__ __forceinline__ void adamw_body(const TensorMeta* __restrict__ metas,
     for (int64_t i = start + threadIdx.x; i < end; i += 256) {
       float p = to_f32(P[i]), m = to_f32(M[i]), v = to_f32(V[i]);
       adamw_elem<TP, TS>(p, to_f32(G[i]) * grad_scale, m, v, lr, b1, b2, eps, wd, bc1, bc2_sqrt);
+      // the fp32 results are final: without this the compiler fuses the last fma of each with the cast to
+      // fp16 below (v_fma_mixlo_f16, one rounding instead of two) in this loop only, and fp16 updates from
+      // the vector and the scalar path differ in the last bit
+      asm("" : "+v"(p), "+v"(m), "+v"(v));
       P[i] = from_f32<TP>(p);
       M[i] = from_f32<TS>(m);
       V[i] = from_f32<TS>(v);

@@ -9,6 +9,7 @@
 // writes (softmax - onehot) * dloss / n_valid in one pass.  Rows are [tokens, vocab]
 // with vocab = 32000 for Llama-2 (64 KB of bf16 per row).
 #include <algorithm>
+#include <initializer_list>
 
 #include "common.h"
 #include "fp8_cvt.h"
@@ -21,9 +22,9 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf
 
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const T* __restrict__ a, const T* __restrict__ b,
-                                                         T* __restrict__ y, int64_t n) {
+                                                         T* __restrict__ y, int64_t n, bool vec) {
   constexpr int V = Vec16<T>::N;
-  const int64_t nv = n / V;
+  const int64_t nv = vec ? n / V : 0;  // !vec (a pointer is not 16-B aligned): the scalar loop takes it all
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
     const Vec16<T> av = load16(a + i * V), bv = load16(b + i * V);
     Vec16<T> o;
@@ -113,9 +114,9 @@ __global__ __launch_bounds__(256) void swiglu_bwd_fp8_kernel(const T* __restrict
 template <typename T>
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ g, const T* __restrict__ a,
                                                          const T* __restrict__ b, T* __restrict__ da,
-                                                         T* __restrict__ db, int64_t n) {
+                                                         T* __restrict__ db, int64_t n, bool vec) {
   constexpr int V = Vec16<T>::N;
-  const int64_t nv = n / V;
+  const int64_t nv = vec ? n / V : 0;  // as in swiglu_fwd_kernel
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
     const Vec16<T> gv = load16(g + i * V), av = load16(a + i * V), bv = load16(b + i * V);
     Vec16<T> oa, ob;
@@ -136,6 +137,12 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const T* __restrict__ g
     da[i] = from_f32<T>(gg * bb * (s * (1.f + x * (1.f - s))));
     db[i] = from_f32<T>(gg * x * s);
   }
+}
+
+bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if ((uintptr_t)p % 16) return false;
+  return true;
 }
 
 int ew_grid(int64_t n_items) {
@@ -172,11 +179,14 @@ __global__ __launch_bounds__(kCeThreads) void ce_fwd_kernel(const T* __restrict_
 #pragma unroll
       for (int j = 0; j < VEC; ++j) lm = fmaxf(lm, to_f32(xv.v[j]));
       const float nm = fmaxf(m, lm);
-      float acc = s * __expf(m - nm);
+      // nothing finite seen yet: -inf - (-inf) is NaN, so rescale against 0 (every exp is then exp(-inf) = 0),
+      // the guard the cross-thread combine below has
+      const float ref = (nm == -INFINITY) ? 0.f : nm;
+      float acc = s * __expf(m - ref);
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         const float f = to_f32(xv.v[j]);
-        acc += __expf(f - nm);
+        acc += __expf(f - ref);
         if (wsm) {
           sum_x += weight[i + j] * f;
           sum_w += weight[i + j];
@@ -191,7 +201,8 @@ __global__ __launch_bounds__(kCeThreads) void ce_fwd_kernel(const T* __restrict_
     for (int i = threadIdx.x; i < V; i += kCeThreads) {
       const float f = to_f32(x[i]);
       const float nm = fmaxf(m, f);
-      s = s * __expf(m - nm) + __expf(f - nm);
+      const float ref = (nm == -INFINITY) ? 0.f : nm;  // as in the vector loop
+      s = s * __expf(m - ref) + __expf(f - ref);
       m = nm;
       if (wsm) {
         sum_x += weight[i] * f;
@@ -318,7 +329,7 @@ __global__ __launch_bounds__(kCeThreads) void ce_bwd_kernel(const T* __restrict_
 
 LTA_EXPORT int lta_swiglu_fwd(int dtype, const void* a, const void* b, void* y, int64_t n, hipStream_t stream) {
   LTA_DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_fwd_kernel<T>), dim3(ew_grid(n / Vec16<T>::N + 1)), dim3(256), 0,
-                                           stream, (const T*)a, (const T*)b, (T*)y, n));
+                                           stream, (const T*)a, (const T*)b, (T*)y, n, aligned16({a, b, y})));
   return (int)hipGetLastError();
 }
 
@@ -361,7 +372,8 @@ LTA_EXPORT int lta_swiglu_bwd_fp8(int dtype, const void* g, const void* a, const
 LTA_EXPORT int lta_swiglu_bwd(int dtype, const void* g, const void* a, const void* b, void* da, void* db, int64_t n,
                               hipStream_t stream) {
   LTA_DISPATCH_T(dtype, hipLaunchKernelGGL((swiglu_bwd_kernel<T>), dim3(ew_grid(n / Vec16<T>::N + 1)), dim3(256), 0,
-                                           stream, (const T*)g, (const T*)a, (const T*)b, (T*)da, (T*)db, n));
+                                           stream, (const T*)g, (const T*)a, (const T*)b, (T*)da, (T*)db, n,
+                                           aligned16({g, a, b, da, db})));
   return (int)hipGetLastError();
 }
 

@@ -23,6 +23,8 @@ def rms_norm_fwd(x: torch.Tensor, weight: torch.Tensor | None, eps: float):
     w = None if weight is None else weight.contiguous()
     y = torch.empty_like(x2)
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    if rows == 0:  # nothing to launch (a zero-size grid is an error)
+        return y.view(x.shape), rstd
     rc = lib.lta_rmsnorm_fwd(dcode(x2), ptr(x2), ptr(w), ptr(y), ptr(rstd), rows, cols, float(eps), stream_ptr(x.device))
     check(rc, "lta_rmsnorm_fwd")
     return y.view(x.shape), rstd
@@ -75,6 +77,8 @@ def layer_norm_fwd(x: torch.Tensor, weight, bias, eps: float):
     y = torch.empty_like(x2)
     mean = torch.empty(rows, device=x.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
+    if rows == 0:  # nothing to launch (a zero-size grid is an error)
+        return y.view(x.shape), mean, rstd
     check(lib.lta_layernorm_fwd(dcode(x2), ptr(x2), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, cols,
                                 float(eps), stream_ptr(x.device)), "lta_layernorm_fwd")
     return y.view(x.shape), mean, rstd

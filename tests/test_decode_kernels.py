@@ -22,13 +22,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-gpu = pytest.mark.gpu
+from kernel_checks import ABS_FLOOR, BF16, F16, F32, ULP, _dt_id, assert_within, bits_equal
 
-BF16, F16, F32 = torch.bfloat16, torch.float16, torch.float32
-ULP = {BF16: 2.0 ** -8, F16: 2.0 ** -10, F32: 2.0 ** -23}
-E32_FACTOR = 8.0
-ABS_FLOOR = 1e-6
-_INT_VIEW = {BF16: torch.int16, F16: torch.int16, F32: torch.int32}
+gpu = pytest.mark.gpu
 
 # Largest err / tol measured on MI355X per group, bf16 / fp16 / fp32 (every run prints them with -s):
 #   decode attention   0.99 / 0.49         (rows4/rising, rows4/leftpad)
@@ -37,35 +33,6 @@ _INT_VIEW = {BF16: torch.int16, F16: torch.int16, F32: torch.int32}
 # 2^-8 |x| is exactly the largest half-spacing of bf16 (reached just above a power of two), so a
 # correctly rounded bf16 output sits at up to 1.0 of the first term alone; fp16 (spacing 2^-10 |x| at
 # most, half of it the rounding) at up to 0.5.  No case needed more than the factor 8.
-_WORST: dict = {}
-
-
-def _dt_id(d):
-    return str(d).replace("torch.", "")
-
-
-def assert_within(out, ref64, ref32, dtype, group, what=""):
-    """|out - ref64| <= ulp(T) |ref64| + 8 e32 + 1e-6 for every element; records the worst ratio."""
-    assert out.shape == ref64.shape, (out.shape, ref64.shape)
-    assert torch.isfinite(ref64).all(), f"{what}: reference is not finite"
-    e32 = (ref32.double() - ref64).abs().max().item()
-    tol = ULP[dtype] * ref64.abs() + E32_FACTOR * e32 + ABS_FLOOR
-    err = (out.double() - ref64).abs()
-    assert not torch.isnan(err).any(), f"{what}: NaN in the kernel output"
-    ratio = (err / tol).max().item()
-    key = (group, _dt_id(dtype))
-    _WORST[key] = max(_WORST.get(key, 0.0), ratio)
-    off = (out != ref64.to(dtype)).sum().item()  # elements that are not the correctly rounded reference
-    print(f"[{group} {_dt_id(dtype)}] {what} err/tol={ratio:.3f} max_err={err.max().item():.3e} e32={e32:.3e}"
-          f" off_by_rounding={off}/{out.numel()} (worst so far {_WORST[key]:.3f})")
-    assert ratio <= 1.0, f"{what}: err/tol = {ratio:.3f} (max err {err.max().item():.3e}, e32 {e32:.3e})"
-
-
-def bits_equal(a, b):
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    it = _INT_VIEW[a.dtype]
-    return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
 
 
 # ------------------------------------------------------------------------------------------------
