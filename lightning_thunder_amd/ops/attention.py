@@ -117,7 +117,7 @@ def _qkv_in_place(q, k, v):
     """q / k / v as the kernels read them: any [B, H, T] strides with the head dim contiguous and
     16-byte aligned rows in place (e.g. views into a fused qkv projection), else a contiguous copy;
     plus their (batch, head, token) strides for the kernels."""
-    q, k, v = (t if _rows_ok(t) else t.contiguous() for t in (q, k, v))
+    q, k, v = (_rows_in_place(t) for t in (q, k, v))
     st = (ctypes.c_int64 * 9)(*q.stride()[:3], *k.stride()[:3], *v.stride()[:3])
     return q, k, v, st
 
@@ -134,6 +134,14 @@ def _grad_like(t):
 def _rows_ok(t) -> bool:
     """Head dim contiguous, 16-byte aligned rows: any [B, H, T] strides are read in place."""
     return t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
+
+
+def _rows_in_place(t):
+    """``t`` itself when the kernels can read it in place, else a dense copy in fresh (aligned) memory:
+    ``contiguous()`` alone hands a dense tensor at a misaligned address back as it is."""
+    if _rows_ok(t):
+        return t
+    return t.clone(memory_format=torch.contiguous_format) if t.is_contiguous() else t.contiguous()
 
 
 register_signature("lta_attn_set_rng_state", [c_void_p])
@@ -218,8 +226,7 @@ def attn_bwd(do, q, k, v, o, lse, causal: bool, scale: float | None = None, mask
                        dropout_p, seed, offset, mask_grad)
         return (res[0][..., :D0], res[1][..., :D0], res[2][..., :D0]) + tuple(res[3:])
     q, k, v, qkv_st = _qkv_in_place(q, k, v)
-    do = do if _rows_ok(do) else do.contiguous()
-    o = o if _rows_ok(o) else o.contiguous()
+    do, o = _rows_in_place(do), _rows_in_place(o)
     B, Hq, T, D = q.shape
     Hkv, S = k.shape[1], k.shape[2]
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -233,7 +240,9 @@ def attn_bwd(do, q, k, v, o, lse, causal: bool, scale: float | None = None, mask
     dmask = None
     if mask_grad:
         assert mask is not None and mask.dtype != torch.bool
-        dmask = torch.empty((B, Hq, T, S), device=q.device, dtype=torch.float32)
+        # causal: the dK/dV kernel skips the query tiles wholly above the diagonal and never stores their
+        # (zero) dS, so those entries must not be left uninitialised
+        dmask = (torch.zeros if causal else torch.empty)((B, Hq, T, S), device=q.device, dtype=torch.float32)
     seed, offset = _graph_rng(lib, dropout_p, seed, offset)
     part = None
     if Hq > Hkv and mask is None and dropout_p == 0:
@@ -324,8 +333,7 @@ def attn_bwd_rope(do, q, k, v, o, lse, causal: bool, scale, cos, sin, n_head: in
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
     if D == 128 and S == T and Hq == n_head and Hkv == n_query_groups:
         qq, kk, vv, qkv_st = _qkv_in_place(q, k, v)
-        dd = do if _rows_ok(do) else do.contiguous()
-        oo = o if _rows_ok(o) else o.contiguous()
+        dd, oo = _rows_in_place(do), _rows_in_place(o)
         cs = cos[:T].float().contiguous()
         sn = sin[:T].float().contiguous()
         W = (Hq + 2 * Hkv) * D
@@ -379,8 +387,7 @@ DECODE_MAX_QUERIES = 16
 
 def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
     """Head dim contiguous and every row start 16-byte aligned (the kernel uses 16-byte loads)."""
-    ok = t.stride(-1) == 1 and all(s % 8 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0
-    return t if ok else t.contiguous()
+    return _rows_in_place(t)
 
 
 def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = None):

@@ -286,7 +286,9 @@ __global__ __launch_bounds__(kThreads, 1) void attn_bwd_dkdv_kernel(const T* __r
       *reinterpret_cast<uint4*>(dOt + row * C::TSTR + ch * 8) = xo;
     }
     if (tid < kQT) {
-      const bool ok = qbase + tid < Tq;
+      // a fully masked row (the forward's lse = -inf, O = 0) contributes p = 0 like a row past Tq:
+      // exp2f(-inf - -inf) would be NaN
+      const bool ok = qbase + tid < Tq && !(MASK && plse == -INFINITY);
       s_lse[buf][tid] = ok ? plse * 1.44269504088896340736f : INFINITY;
       s_delta[buf][tid] = ok ? pdel : 0.f;
       if constexpr (DROP) s_qterm[buf][tid] = rng_q(rng_head(ex, b * Hq + hbase + it / nq), qbase + tid);
@@ -957,7 +959,9 @@ __global__ __launch_bounds__(kThreads, (EX || D > 128) ? 1 : 2) void attn_bwd_dq
     qf[s] = load_frag<F>(Qb + (int64_t)qrow * ex.sx.qt + 16 * s + 8 * h);
     of[s] = load_frag<F>(dOb + qrow * sdo.t + 16 * s + 8 * h);
   }
-  const float lse2 = LSE[((int64_t)b * Hq + hq) * Tq + qrow] * 1.44269504088896340736f;
+  float lse2 = LSE[((int64_t)b * Hq + hq) * Tq + qrow] * 1.44269504088896340736f;
+  // a fully masked row (the forward's lse = -inf): p = exp2f(s - inf) = 0, not exp2f(-inf - -inf) = NaN
+  if constexpr (MASK) lse2 = (lse2 == -INFINITY) ? INFINITY : lse2;
   const float dlt = DELTA[((int64_t)b * Hq + hq) * Tq + qrow];
   const float* mrow = nullptr;
   if constexpr (MASK) mrow = ex.mask + b * ex.mb + hq * ex.mh + (int64_t)qrow * ex.mq;

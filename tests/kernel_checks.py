@@ -1,4 +1,5 @@
-"""Shared assertions of the kernel-against-fp64 batteries (test_decode_kernels.py, test_train_row_kernels.py).
+"""Shared assertions of the kernel-against-fp64 batteries (test_decode_kernels.py, test_train_row_kernels.py,
+test_attention_kernels.py) and the mirror of the attention kernels' dropout hash.
 
 Tolerance of every rounded output, per element:  ulp(T) * |ref64| + 8 * e32 + floor.
 ``ulp`` is the spacing of T at 1 (2^-8 bf16, 2^-10 fp16, 2^-23 fp32): the single rounding of the
@@ -6,7 +7,7 @@ output.  ``e32`` is the largest error of a plain torch fp32 evaluation of the sa
 the same inputs; the kernels accumulate in fp32, and the factor 8 covers their fast exp and their
 summation order.  ``floor`` is 1e-6, or with ``rel_floor`` 1e-6 * max |ref64| (outputs that are small
 as a whole: Adam second moments, gradients under a mean); a reference that is zero everywhere then
-asks for exact zeros, and the rounding term is at least half the subnormal spacing of T (fp16: 2^-25 =
+asks for exact zeros (unless the caller's error model adds an ``extra`` term: that is then the tolerance), and the rounding term is at least half the subnormal spacing of T (fp16: 2^-25 =
 3e-8; without it a correctly rounded fp16 value below 6e-5 fails ulp(T) |ref64|).
 """
 import torch
@@ -26,13 +27,14 @@ def _dt_id(d):
     return str(d).replace("torch.", "")
 
 
-def assert_within(out, ref64, ref32, dtype, group, what="", rel_floor=False):
-    """|out - ref64| <= ulp(T) |ref64| + 8 e32 + floor for every element; records the worst ratio."""
+def assert_within(out, ref64, ref32, dtype, group, what="", rel_floor=False, extra=None):
+    """|out - ref64| <= ulp(T) |ref64| + 8 e32 + floor (+ ``extra``, a per-element term of the caller's
+    error model) for every element; records the worst ratio."""
     assert out.shape == ref64.shape, (out.shape, ref64.shape)
     assert torch.isfinite(ref64).all(), f"{what}: reference is not finite"
     if out.numel() == 0:
         return
-    if rel_floor and not ref64.any():
+    if rel_floor and extra is None and not ref64.any():
         assert not out.double().abs().any(), f"{what}: the reference is zero everywhere, the output is not"
         print(f"[{group} {_dt_id(dtype)}] {what} exact zeros")
         return
@@ -42,6 +44,9 @@ def assert_within(out, ref64, ref32, dtype, group, what="", rel_floor=False):
     if rel_floor:  # below its smallest normal T is spaced absolutely: a correctly rounded fp16 is off by up to 2^-25
         rounding = rounding.clamp(min=HALF_SUBNORMAL[dtype])
     tol = rounding + E32_FACTOR * e32 + floor
+    if extra is not None:
+        assert extra.shape == ref64.shape and (extra >= 0).all(), f"{what}: malformed extra tolerance term"
+        tol = tol + extra.double()
     err = (out.double() - ref64).abs()
     assert not torch.isnan(err).any(), f"{what}: NaN in the kernel output"
     ratio = (err / tol).max().item()
@@ -51,6 +56,36 @@ def assert_within(out, ref64, ref32, dtype, group, what="", rel_floor=False):
     print(f"[{group} {_dt_id(dtype)}] {what} err/tol={ratio:.3f} max_err={err.max().item():.3e} e32={e32:.3e}"
           f" off_by_rounding={off}/{out.numel()} (worst so far {_WORST[key]:.3f})")
     assert ratio <= 1.0, f"{what}: err/tol = {ratio:.3f} (max err {err.max().item():.3e}, e32 {e32:.3e})"
+
+
+M32 = 0xFFFFFFFF
+
+
+def _fmix32(h):
+    h = h & M32
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & M32
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & M32
+    h = h ^ (h >> 16)
+    return h
+
+
+def keep_mask(seed, offset, B, H, T, S, p, device):
+    """The attention kernels' dropout keep mask [B, H, T, S] (True = kept): a mirror of attention.h
+    rng_head / rng_q / rng_k / rng_keep in int64 torch arithmetic."""
+    lo, hi = seed & M32, (seed >> 32) & M32
+    base = _fmix32(torch.tensor(lo ^ ((offset * 0x27D4EB2F) & M32), dtype=torch.int64, device=device)) ^ hi
+    bh = torch.arange(B * H, dtype=torch.int64, device=device)
+    head = _fmix32(((bh * 0x9E3779B9) & M32) ^ base)  # [BH]
+    q = torch.arange(T, dtype=torch.int64, device=device)
+    k = torch.arange(S, dtype=torch.int64, device=device)
+    qterm = _fmix32(((q[None, :] * 0x61C88647) & M32) + head[:, None])  # [BH, T]
+    kterm = _fmix32(((k * 0x7FEB352D) & M32) + 0x3C6EF372)  # [S]
+    h = _fmix32(qterm[:, :, None] ^ kterm[None, None, :])
+    p32 = float(torch.tensor(p, dtype=torch.float32))  # the kernels receive p as fp32
+    thresh = min(int(p32 * 4294967296.0), 4294967295)
+    return (h >= thresh).reshape(B, H, T, S)
 
 
 def bits_equal(a, b):

@@ -3,43 +3,17 @@ reference: cuDNN SDPA masks + dropout, thunder/executors/cudnn_sdpa.py; aten fla
 thunder/executors/sdpaex.py:274-336).
 
 Numerics are compared against an fp32 PyTorch reference of the same op.  For dropout the reference
-regenerates the kernels' keep mask from the same counter-based hash (mirrored below in int64 torch
-arithmetic), so forward AND gradients are checked exactly, not statistically.
+regenerates the kernels' keep mask from the same counter-based hash (mirrored in kernel_checks.py in int64
+torch arithmetic), so forward AND gradients are checked exactly, not statistically.
 """
 import math
 
 import pytest
 import torch
 
+from kernel_checks import M32, _fmix32, keep_mask  # noqa: F401  (moved there; other files import them from here)
+
 pytestmark = pytest.mark.gpu
-
-M32 = 0xFFFFFFFF
-
-
-def _fmix32(h):
-    h = h & M32
-    h = h ^ (h >> 16)
-    h = (h * 0x85EBCA6B) & M32
-    h = h ^ (h >> 13)
-    h = (h * 0xC2B2AE35) & M32
-    h = h ^ (h >> 16)
-    return h
-
-
-def keep_mask(seed, offset, B, H, T, S, p, device):
-    """Mirror of attention.h rng_head / rng_q / rng_k / rng_keep."""
-    lo, hi = seed & M32, (seed >> 32) & M32
-    base = _fmix32(torch.tensor(lo ^ ((offset * 0x27D4EB2F) & M32), dtype=torch.int64, device=device)) ^ hi
-    bh = torch.arange(B * H, dtype=torch.int64, device=device)
-    head = _fmix32(((bh * 0x9E3779B9) & M32) ^ base)  # [BH]
-    q = torch.arange(T, dtype=torch.int64, device=device)
-    k = torch.arange(S, dtype=torch.int64, device=device)
-    qterm = _fmix32(((q[None, :] * 0x61C88647) & M32) + head[:, None])  # [BH, T]
-    kterm = _fmix32(((k * 0x7FEB352D) & M32) + 0x3C6EF372)  # [S]
-    h = _fmix32(qterm[:, :, None] ^ kterm[None, None, :])
-    p32 = float(torch.tensor(p, dtype=torch.float32))  # the kernels receive p as fp32
-    thresh = min(int(p32 * 4294967296.0), 4294967295)
-    return (h >= thresh).reshape(B, H, T, S)
 
 
 def ref_attn(q, k, v, mask=None, causal=False, keep=None, p=0.0, scale=None):
