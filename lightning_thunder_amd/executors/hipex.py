@@ -8,14 +8,17 @@ what the fused backward kernels need (e.g. RMSNorm's per-row rstd, attention's L
 from __future__ import annotations
 
 import math
+import os
+from functools import partial
+from typing import Callable, NamedTuple
 
 import torch
 
 from ..core.prims import OpTags
 from ..core.proxies import TensorProxy, pyval
 from ..core import dtypes
-from ..core.pytree import tree_flatten
 from ..extend import OperatorExecutor, register_executor, add_default_executor
+from .rewrite import Rewrite, operands
 
 ex = OperatorExecutor("hipex", version="0.1")
 register_executor(ex)
@@ -258,6 +261,20 @@ hip_swiglu_fp8 = ex.register_operator("hip_swiglu_fp8", meta=lambda a, b, key, s
                                       fn=_swiglu_fp8_impl)
 
 
+def _delayed_cast(b, e5m2: bool):
+    """The operands of ``b`` when it is the delayed-scaling row cast to e5m2 (gradients) / e4m3, else None."""
+    if b.sym is not hip_fp8_cast_delayed:
+        return None
+    c = operands(b)
+    return c if bool(c["e5m2"]) == e5m2 and c["key"] is not None else None
+
+
+def _fp8_producer_fusion_off() -> bool:
+    import os
+
+    return os.environ.get("LTA_FP8_FUSE_PRODUCERS", "1") == "0"  # A/B hook
+
+
 def _fuse_fp8_cast_producers(trace):
     """``y, rstd = hip_rms_norm_fwd(x, w, eps); q, s = hip_fp8_cast_delayed(y, False, key, slot)`` ->
     ``q, s, rstd = hip_rms_norm_fwd_fp8(x, w, eps, key, slot)``, and ``y = hip_swiglu(a, b)`` + its
@@ -265,66 +282,48 @@ def _fuse_fp8_cast_producers(trace):
     leaves the producing kernel as e4m3 (no bf16 round trip, no separate cast launch).  Parity: the
     reference's TransformerEngine layers quantise inside their fused norm / activation kernels
     (thunder/executors/transformer_engineex_impl.py)."""
-    import os
-
-    from ..core.trace import from_trace, TraceProvenance
-
-    if os.environ.get("LTA_FP8_FUSE_PRODUCERS", "1") == "0":  # A/B hook
+    if _fp8_producer_fusion_off():
         return trace
-    bsyms = trace.bound_symbols
-    uses: dict[str, int] = {}
-    for b in bsyms:
-        for a in b.flat_proxy_args:
-            uses[a.name] = uses.get(a.name, 0) + 1
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_fp8_cast_delayed or len(b.args) != 4 or b.args[1]:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        c = _delayed_cast(b, e5m2=False)
+        if c is None:
             continue
-        y, _, key, slot = b.args
-        j = producer.get(y.name)
-        if j is None or j in replace or j in drop or uses.get(y.name, 0) != 1:
+        y = c["t"]
+        j = rw.producer(y)
+        if j is None or rw.touched(j) or rw.uses(y) != 1:
             continue
-        pb = bsyms[j]
-        if pb.sym is hip_rms_norm_fwd and len(pb.args) >= 3 and pb.args[1] is not None and pb.output[0].name == y.name:
-            nb = hip_rms_norm_fwd_fp8.bind(pb.args[0], pb.args[1], pb.args[2], key, slot,
+        pb = rw.bsyms[j]
+        p = operands(pb)
+        if pb.sym is hip_rms_norm_fwd and p["weight"] is not None and pb.output[0].name == y.name:
+            nb = hip_rms_norm_fwd_fp8.bind(p["x"], p["weight"], p["eps"], c["key"], c["slot"],
                                            output=(b.output[0], b.output[1], pb.output[1]))
-        elif pb.sym is hip_swiglu and len(pb.args) == 2:
-            nb = hip_swiglu_fp8.bind(pb.args[0], pb.args[1], key, slot, output=b.output)
+        elif pb.sym is hip_swiglu:
+            nb = hip_swiglu_fp8.bind(p["a"], p["b"], c["key"], c["slot"], output=b.output)
         else:
             continue
-        replace[j] = ex.bind_call_ctx(nb)
-        drop.add(i)
+        rw.replace(j, nb)
+        rw.drop(i)
     # backward: da, db = hip_swiglu_bwd(g, a, b) whose only uses are their e5m2 casts
-    casts: dict[str, int] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is hip_fp8_cast_delayed and len(b.args) == 4 and b.args[1] and i not in drop:
-            casts[b.args[0].name] = i
-    for j, pb in enumerate(bsyms):
-        if pb.sym is not hip_swiglu_bwd or j in replace or len(pb.args) != 3:
+    casts = {}
+    for i, b in enumerate(rw.bsyms):
+        c = _delayed_cast(b, e5m2=True)
+        if c is not None:
+            casts[c["t"].name] = (i, c)
+    for j, pb in enumerate(rw.bsyms):
+        if pb.sym is not hip_swiglu_bwd or rw.touched(j):
             continue
         da, db = pb.output
-        ia, ib = casts.get(da.name), casts.get(db.name)
-        if ia is None or ib is None or uses.get(da.name, 0) != 1 or uses.get(db.name, 0) != 1:
+        if da.name not in casts or db.name not in casts or rw.uses(da) != 1 or rw.uses(db) != 1:
             continue
-        ca, cb = bsyms[ia], bsyms[ib]
-        if ca.args[2] != cb.args[2]:
+        (ia, ca), (ib, cb) = casts[da.name], casts[db.name]
+        if ca["key"] != cb["key"]:
             continue
-        nb = hip_swiglu_bwd_fp8.bind(*pb.args, ca.args[2], ca.args[3], cb.args[3],
-                                     output=(ca.output[0], ca.output[1], cb.output[0], cb.output[1]))
-        replace[j] = ex.bind_call_ctx(nb)
-        drop.update((ia, ib))
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} fp8 input cast(s) fused into their producers"))
-    return new
+        p = operands(pb)
+        rw.replace(j, hip_swiglu_bwd_fp8.bind(p["g"], p["a"], p["b"], ca["key"], ca["slot"], cb["slot"],
+                                              output=(*rw.bsyms[ia].output, *rw.bsyms[ib].output)))
+        rw.drop(ia, ib)
+    return rw.finish(f"hipex: {rw.replaced} fp8 input cast(s) fused into their producers")
 
 
 def _fp8_transposed() -> bool:
@@ -515,84 +514,60 @@ def _register_fp8():
 _register_fp8()
 
 
+def _residual_adds(b):
+    """``(y, r)`` and ``(r, y)`` when ``b`` is ``y + r`` of two tensors of its output's shape (no alpha)."""
+    if b.sym.name not in ("torch_add", "add") or b.kwargs.get("alpha") not in (None, 1):
+        return ()
+    if len(b.args) < 2 or not all(isinstance(a, TensorProxy) for a in b.args[:2]):
+        return ()
+    y, r = b.args[:2]
+    if tuple(r.shape) != tuple(y.shape) or r.dtype != y.dtype or tuple(b.output.shape) != tuple(y.shape):
+        return ()
+    return (y, r), (r, y)
+
+
 def _fuse_linear_epilogues(trace):
     """``y = hip_linear(x, w, b); z = y + r`` (y used nowhere else) -> ``z = hip_linear(x, w, b, r)``:
     the residual add runs in the GEMM's epilogue (one HBM round trip of y saved)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = trace.bound_symbols
-    uses: dict[str, int] = {}
-    for b in bsyms:
-        for a in b.flat_proxy_args:
-            uses[a.name] = uses.get(a.name, 0) + 1
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym.name not in ("torch_add", "add") or b.kwargs.get("alpha") not in (None, 1):
-            continue
-        if len(b.args) < 2 or not all(isinstance(a, TensorProxy) for a in b.args[:2]):
-            continue
-        for pos in (0, 1):
-            y, r = b.args[pos], b.args[1 - pos]
-            j = producer.get(y.name)
-            if (j is None or j in drop or bsyms[j].sym not in (hip_linear, hip_matmul, hip_fp8_gemm, hip_fp8_gemm_layout)
-                    or uses.get(y.name, 0) != 1):
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        for y, r in _residual_adds(b):
+            j = rw.producer(y)
+            if j is None or rw.touched(j) or rw.uses(y) != 1:
                 continue
-            lb = bsyms[j]
-            if tuple(r.shape) != tuple(y.shape) or r.dtype != y.dtype or tuple(b.output.shape) != tuple(y.shape):
+            lb = rw.bsyms[j]
+            if lb.sym not in (hip_linear, hip_matmul, hip_fp8_gemm, hip_fp8_gemm_layout):
                 continue
-            if lb.sym is hip_fp8_gemm_layout:
-                if lb.args[5] or (len(lb.args) > 7 and lb.args[7] is not None) or "residual" in lb.kwargs:
-                    continue  # the residual epilogue exists for the dgrad layout (A [M][K]) only
-                if producer.get(r.name, -1) > i or j in replace:
-                    continue
-                replace[i] = ex.bind_call_ctx(hip_fp8_gemm_layout.bind(*lb.args[:7], r, output=b.output))
-                drop.add(j)
-                break
-            if lb.sym is hip_fp8_gemm:
-                if len(lb.args) > 8 and lb.args[8] is not None or "residual" in lb.kwargs:
-                    continue
-                if producer.get(r.name, -1) > i or j in replace:
-                    continue
-                # computed where the add was (every input of the GEMM exists there)
-                nb = ex.bind_call_ctx(hip_fp8_gemm.bind(*lb.args[:8], r, output=b.output))
-                replace[i] = nb
-                drop.add(j)
-                break
-            if producer.get(r.name, -1) > j:
-                continue  # the residual is produced after the GEMM: the fused op could not see it
-            if lb.sym is hip_matmul:
-                if len(lb.args) > 2 and lb.args[2] is not None:
-                    continue
-                nb = hip_matmul.bind(lb.args[0], lb.args[1], r, output=b.output)
-                nb = ex.bind_call_ctx(nb)
-                replace[j] = nb  # computed where the GEMM was (the add's consumers come later)
-                drop.add(i)
-                break
-            if len(lb.args) > 3 and lb.args[3] is not None:
+            p = operands(lb)
+            if p["residual"] is not None or p.get("act") is not None or p.get("at"):
+                continue  # the fp8 layout GEMM has its residual epilogue for the dgrad layout (A [M][K]) only
+            # hip_matmul is computed where the GEMM was (the add's consumers come later), the others where
+            # the add was (every input of the GEMM exists there); the residual must exist at that place
+            at, gone = (j, i) if lb.sym is hip_matmul else (i, j)
+            if rw.producer(r, -1) > (i if lb.sym in (hip_fp8_gemm, hip_fp8_gemm_layout) else j):
                 continue
-            bias = lb.args[2] if len(lb.args) > 2 else lb.kwargs.get("bias")
-            nb = hip_linear.bind(lb.args[0], lb.args[1], bias, r, output=b.output)
-            nb = ex.bind_call_ctx(nb)
-            replace[i] = nb
-            drop.add(j)
+            head = list(p.values())[:list(p).index("residual")]
+            rw.replace(at, lb.sym.bind(*head, r, output=b.output))
+            rw.drop(gone)
             break
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} residual add(s) fused into GEMM epilogues"))
-    return new
+    return rw.finish(f"hipex: {rw.replaced} residual add(s) fused into GEMM epilogues")
 
 
 # =========================================================================================
 # K2b decode GEMV with fused prologues (rmsnorm) / gated epilogues (SwiGLU up-projection pair)
 # =========================================================================================
+def _as_rows(x, residual=None):
+    """x as [rows, K] and the residual, if any, as [rows, N]: what the decode launchers take."""
+    return x.reshape(-1, x.shape[-1]), None if residual is None else residual.reshape(-1, residual.shape[-1])
+
+
+def _like(x, outs, packed=True):
+    """Row results back under x's leading dims: one tensor (a single or packed launch) or one per weight."""
+    if packed:
+        return outs.reshape(*x.shape[:-1], outs.shape[-1])
+    return tuple(o.reshape(*x.shape[:-1], o.shape[-1]) for o in outs)
+
+
 def _decode_linear_meta(x, w, bias=None, residual=None, act=None, gate_weight=None, norm=False, norm_weight=None,
                         eps=1e-5):
     return TensorProxy(like=x, shape=tuple(x.shape[:-1]) + (w.shape[0],))
@@ -602,16 +577,13 @@ def _decode_linear_impl(x, w, bias=None, residual=None, act=None, gate_weight=No
                         eps=1e-5):
     from ..ops.gemm import gemv_nt, gemv_supported, _torch_linear
 
-    K, N = x.shape[-1], w.shape[0]
-    x2 = x.reshape(-1, K)
-    r2 = None if residual is None else residual.reshape(-1, N)
+    x2, r2 = _as_rows(x, residual)
     ok = gemv_supported(x2, w, bias, r2) and (gate_weight is None or gate_weight.stride() == w.stride())
     if ok and norm_weight is not None:
         ok = norm_weight.is_contiguous() and norm_weight.dtype == x.dtype
     if ok:
-        y = gemv_nt(x2, w, bias=bias, residual=r2, act=act, gate_weight=gate_weight, norm=norm,
-                    norm_weight=norm_weight, eps=eps)
-        return y.reshape(*x.shape[:-1], N)
+        return _like(x, gemv_nt(x2, w, bias=bias, residual=r2, act=act, gate_weight=gate_weight, norm=norm,
+                                norm_weight=norm_weight, eps=eps))
     if norm:  # unaligned operands: the same math on the library path
         from ..ops.rmsnorm import rms_norm_fwd
 
@@ -620,7 +592,7 @@ def _decode_linear_impl(x, w, bias=None, residual=None, act=None, gate_weight=No
         y = _torch_linear(x2, w, None, None, act) * torch.nn.functional.linear(x2, gate_weight)
     else:
         y = _torch_linear(x2, w, bias, r2, act)
-    return y.reshape(*x.shape[:-1], N)
+    return _like(x, y)
 
 
 hip_decode_linear = ex.register_operator("hip_decode_linear", meta=_decode_linear_meta, fn=_decode_linear_impl)
@@ -634,139 +606,6 @@ def _rows(t) -> int:
     return r
 
 
-def _linear_parts(b):
-    names = ("x", "w", "bias", "residual", "act")
-    d = dict(zip(names, b.args))
-    d.update({k: v for k, v in b.kwargs.items() if k in names})
-    return d
-
-
-def _fuse_decode_gemv(trace):
-    """Decode-shaped (<= 8 rows) chains around the weight-streaming GEMV, one launch each:
-
-    * ``a = hip_linear(x, w1); b = hip_linear(x, w2); y = hip_swiglu(a, b)`` ->
-      ``y = hip_decode_linear(x, w1, act="silu", gate_weight=w2)`` (LLaMA MLP up-projections + gate);
-    * ``y, rstd = hip_rms_norm_fwd(x, g, eps)`` whose ``y`` only feeds decode linears (and ``rstd``
-      nothing) -> the norm runs in those GEMVs' prologue (``norm=True``).
-    Every launch removed is ~5 us of a ~1 ms decode step on MI355X (kernel floor + boundary)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = list(trace.bound_symbols)
-
-    def count_uses(skip):
-        u: dict[str, int] = {}
-        for k, b in enumerate(bsyms):
-            if k not in skip:
-                for a in b.flat_proxy_args:
-                    u[a.name] = u.get(a.name, 0) + 1
-        for o in tree_flatten(trace.output)[0] if trace.output is not None else ():
-            if isinstance(o, TensorProxy):
-                u[o.name] = u.get(o.name, 0) + 1
-        return u
-
-    uses = count_uses(())
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    n_gated = n_norm = 0
-
-    def bind(i, *args, output, **kwargs):
-        bsyms[i] = ex.bind_call_ctx(hip_decode_linear.bind(*args, output=output, **kwargs))
-
-    # SwiGLU up-projection pairs
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_swiglu or len(b.args) != 2:
-            continue
-        a, g = b.args
-        ja, jg = producer.get(a.name), producer.get(g.name)
-        if ja is None or jg is None or ja in drop or jg in drop or ja == jg:
-            continue
-        la, lg = bsyms[ja], bsyms[jg]
-        if la.sym is not hip_linear or lg.sym is not hip_linear or uses.get(a.name) != 1 or uses.get(g.name) != 1:
-            continue
-        pa, pg = _linear_parts(la), _linear_parts(lg)
-        if pa["x"].name != pg["x"].name or any(p.get(k) is not None for p in (pa, pg) for k in ("bias", "residual", "act")):
-            continue
-        if _rows(pa["x"]) > _GEMV_MAX_ROWS or tuple(pa["w"].shape) != tuple(pg["w"].shape):
-            continue
-        bind(i, pa["x"], pa["w"], None, None, "silu", pg["w"], False, None, 1e-5, output=b.output)
-        drop.update((ja, jg))
-        n_gated += 1
-
-    # the same pair written out (HF LlamaMLP): y = mul(silu(a), b)
-    for i, b in enumerate(bsyms):
-        if i in drop or b.sym.name != "mul" or len(b.args) != 2 or not all(isinstance(a, TensorProxy) for a in b.args):
-            continue
-        for s_arg, g_arg in (b.args, b.args[::-1]):
-            js = producer.get(s_arg.name)
-            if js is None or js in drop or bsyms[js].sym.name != "silu" or uses.get(s_arg.name) != 1:
-                continue
-            sb = bsyms[js]
-            a = sb.args[0] if sb.args else None
-            if len(sb.args) > 1 and sb.args[1] not in (False, None):
-                continue
-            ja, jg = producer.get(getattr(a, "name", None)), producer.get(g_arg.name)
-            if ja is None or jg is None or ja in drop or jg in drop or ja == jg:
-                continue
-            la, lg = bsyms[ja], bsyms[jg]
-            if la.sym is not hip_linear or lg.sym is not hip_linear or uses.get(a.name) != 1 or uses.get(g_arg.name) != 1:
-                continue
-            pa, pg = _linear_parts(la), _linear_parts(lg)
-            if pa["x"].name != pg["x"].name or any(p.get(k) is not None for p in (pa, pg) for k in ("bias", "residual", "act")):
-                continue
-            if _rows(pa["x"]) > _GEMV_MAX_ROWS or tuple(pa["w"].shape) != tuple(pg["w"].shape) or b.output.dtype != a.dtype:
-                continue
-            bind(i, pa["x"], pa["w"], None, None, "silu", pg["w"], False, None, 1e-5, output=b.output)
-            drop.update((ja, jg, js))
-            n_gated += 1
-            break
-
-    # RMSNorm prologues
-    uses = count_uses(drop)
-    for i, b in enumerate(bsyms):
-        if i in drop or b.sym is not hip_rms_norm_fwd:
-            continue
-        y, rstd = b.output
-        x, g, eps = b.args[0], b.args[1], b.args[2]
-        if uses.get(rstd.name, 0) or _rows(x) > _GEMV_MAX_ROWS or not isinstance(eps, (int, float)):
-            continue
-        consumers = [j for j, c in enumerate(bsyms) if j not in drop and any(a.name == y.name for a in c.flat_proxy_args)]
-        ok = bool(consumers)
-        for j in consumers:
-            c = bsyms[j]
-            if c.sym is hip_linear:
-                p = _linear_parts(c)
-                ok = ok and p["x"] is not None and p["x"].name == y.name and p["w"].name != y.name
-            elif c.sym is hip_decode_linear:
-                ok = ok and c.args[0].name == y.name and not c.args[6] and all(
-                    getattr(a, "name", None) != y.name for a in c.args[1:])
-            else:
-                ok = False
-        if not ok or sum(1 for j in consumers) != uses.get(y.name, 0):
-            continue
-        for j in consumers:
-            c = bsyms[j]
-            if c.sym is hip_linear:
-                p = _linear_parts(c)
-                bind(j, x, p["w"], p.get("bias"), p.get("residual"), p.get("act"), None, True, g, float(eps),
-                     output=c.output)
-            else:
-                a = list(c.args)
-                bind(j, x, a[1], a[2], a[3], a[4], a[5], True, g, float(eps), output=c.output)
-        drop.add(i)
-        n_norm += 1
-
-    if not drop:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [b for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: decode GEMV fusion ({n_gated} gated pair(s), {n_norm} norm prologue(s))"))
-    return new
-
-
 def _decode_group_meta(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
     if packed:
         return TensorProxy(like=x, shape=tuple(x.shape[:-1]) + (sum(w.shape[0] for w in weights),))
@@ -776,8 +615,7 @@ def _decode_group_meta(x, weights, norm=False, norm_weight=None, eps=1e-5, packe
 def _decode_group_impl(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
     from ..ops.gemm import gemv_group, gemv_supported
 
-    K = x.shape[-1]
-    x2 = x.reshape(-1, K)
+    x2, _ = _as_rows(x)
     ok = all(gemv_supported(x2, w) for w in weights)
     if ok and norm_weight is not None:
         ok = norm_weight.is_contiguous() and norm_weight.dtype == x.dtype
@@ -791,98 +629,11 @@ def _decode_group_impl(x, weights, norm=False, norm_weight=None, eps=1e-5, packe
         outs = [torch.nn.functional.linear(x2, w) for w in weights]
         if packed:
             outs = torch.cat(outs, -1)
-    if packed:
-        return outs.reshape(*x.shape[:-1], outs.shape[-1])
-    return tuple(o.reshape(*x.shape[:-1], o.shape[-1]) for o in outs)
+    return _like(x, outs, packed)
 
 
 hip_decode_linear_group = ex.register_operator("hip_decode_linear_group", meta=_decode_group_meta,
                                                fn=_decode_group_impl)
-
-
-def _group_decode_projections(trace):
-    """Sibling decode projections of one input (HF attention's q / k / v: ``hip_decode_linear`` or
-    ``hip_linear`` with <= 8 rows, same x and norm prologue, no bias / residual / activation / gate)
-    -> one ``hip_decode_linear_group`` launch streaming all their weights (up to 3 per launch)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = list(trace.bound_symbols)
-    groups: dict = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is hip_decode_linear:
-            a = list(b.args) + [None] * (9 - len(b.args))
-            x, w, bias, res, act, gate, norm, g, eps = a[:9]
-            if any(v is not None for v in (bias, res, act, gate)):
-                continue
-        elif b.sym is hip_linear:
-            p = _linear_parts(b)
-            x, w = p["x"], p["w"]
-            if any(p.get(k) is not None for k in ("bias", "residual", "act")):
-                continue
-            norm, g, eps = False, None, 1e-5
-        else:
-            continue
-        if not isinstance(x, TensorProxy) or _rows(x) > _GEMV_MAX_ROWS or w.ndim != 2:
-            continue
-        key = (x.name, bool(norm), getattr(g, "name", None), float(eps) if isinstance(eps, (int, float)) else eps)
-        groups.setdefault(key, []).append(i)
-    replace: dict[int, object] = {}
-    drop: set[int] = set()
-    n = 0
-    # cat(p0, p1, p2, dim=-1) of sibling projections used only by the cat -> one packed launch
-    uses: dict[str, int] = {}
-    for b in bsyms:
-        for a in b.flat_proxy_args:
-            uses[a.name] = uses.get(a.name, 0) + 1
-    producer = {o.name: i for i, b in enumerate(bsyms) for o in b.flat_proxy_outs}
-    member = {i: key for key, idxs in groups.items() for i in idxs}
-    for ci, cb in enumerate(bsyms):
-        if cb.sym.name not in ("cat", "torch_cat", "cat_prim") or not cb.args or not isinstance(cb.args[0], (list, tuple)):
-            continue
-        parts = cb.args[0]
-        dim = cb.args[1] if len(cb.args) > 1 else cb.kwargs.get("dim", 0)
-        if not 2 <= len(parts) <= 3 or not all(isinstance(p, TensorProxy) for p in parts) or dim not in (-1, parts[0].ndim - 1):
-            continue
-        js = [producer.get(p.name) for p in parts]
-        if any(j is None or j in drop or j in replace or uses.get(p.name) != 1 for j, p in zip(js, parts)):
-            continue
-        keys = {member.get(j) for j in js}
-        if len(keys) != 1 or None in keys:
-            continue
-        (xname, norm, gname, eps), = keys
-        first = bsyms[js[0]]
-        g = (first.args[7] if len(first.args) > 7 else first.kwargs.get("norm_weight")) if norm else None
-        ws = tuple(bsyms[j].args[1] for j in js)
-        replace[ci] = ex.bind_call_ctx(hip_decode_linear_group.bind(first.args[0], ws, norm, g, eps, True,
-                                                                    output=cb.output))
-        drop.update(js)
-        for key_idxs in groups.values():
-            for j in js:
-                if j in key_idxs:
-                    key_idxs.remove(j)
-        n += 1
-    for (xname, norm, gname, eps), idxs in groups.items():
-        for c0 in range(0, len(idxs) - 1, 3):
-            chunk = idxs[c0:c0 + 3]
-            if len(chunk) < 2:
-                continue
-            first = bsyms[chunk[0]]
-            x = first.args[0]
-            g = None
-            if norm:
-                g = first.args[7] if len(first.args) > 7 else first.kwargs.get("norm_weight")
-            ws = tuple(bsyms[j].args[1] for j in chunk)
-            outs = tuple(bsyms[j].output for j in chunk)
-            replace[chunk[0]] = ex.bind_call_ctx(hip_decode_linear_group.bind(x, ws, norm, g, eps, output=outs))
-            drop.update(chunk[1:])
-            n += 1
-    if not n:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {n} grouped decode projection launch(es)"))
-    return new
 
 
 # =========================================================================================
@@ -897,15 +648,13 @@ def _mxfp4_decode_linear_impl(x, q, s, bias=None, residual=None, act=None, gate_
                               norm_weight=None, eps=1e-5):
     from ..ops import mxfp4 as mx
 
-    K, N = x.shape[-1], q.shape[0]
-    x2 = x.reshape(-1, K)
-    r2 = None if residual is None else residual.reshape(-1, N)
+    x2, r2 = _as_rows(x, residual)
     kw = dict(bias=bias, residual=r2, act=act, gate_q=gate_q, gate_s=gate_s)
     if mx.gemv_fused_supported(x2, q, s, norm_weight=norm_weight, **kw):
         y = mx.gemv_fused(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps, **kw)
     else:  # operands the kernel does not take (alignment, > 8 rows): the same math in torch
         y = mx.gemv_fused_reference(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps, **kw)
-    return y.reshape(*x.shape[:-1], N)
+    return _like(x, y)
 
 
 def _mxfp4_decode_group_meta(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
@@ -917,16 +666,14 @@ def _mxfp4_decode_group_meta(x, weights, norm=False, norm_weight=None, eps=1e-5,
 def _mxfp4_decode_group_impl(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
     from ..ops import mxfp4 as mx
 
-    x2 = x.reshape(-1, x.shape[-1])
+    x2, _ = _as_rows(x)
     if all(mx.gemv_fused_supported(x2, q, s, norm_weight=norm_weight) for q, s in weights):
         outs = mx.gemv_group(x2, list(weights), norm=norm, norm_weight=norm_weight, eps=eps, packed=packed)
     else:
         outs = [mx.gemv_fused_reference(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps) for q, s in weights]
         if packed:
             outs = torch.cat(outs, -1)
-    if packed:
-        return outs.reshape(*x.shape[:-1], outs.shape[-1])
-    return tuple(o.reshape(*x.shape[:-1], o.shape[-1]) for o in outs)
+    return _like(x, outs, packed)
 
 
 hip_mxfp4_decode_linear = ex.register_operator("hip_mxfp4_decode_linear", meta=_mxfp4_decode_linear_meta,
@@ -940,233 +687,228 @@ _MXFP4_NORM_MAX_ROWS = 1
 _MXFP4_LINEAR_IDS = ("custom_op.lta::mxfp4_linear", "custom_op.custom_op_impl_custom_op_lta_mxfp4_linear")
 
 
-def _fuse_mxfp4_decode(trace):
-    """``lta::mxfp4_linear`` on <= 8 bf16 rows (4-bit decode) -> ``hip_mxfp4_decode_linear``, with what
-    the bf16 decode GEMV carries folded into the launch:
+# =========================================================================================
+# Decode fusion: one rewrite for both weight kinds, over operand records of the candidate projections
+# =========================================================================================
+def _decode_record(b, x, w, bias=None, residual=None, act=None, gate=None, norm=False, norm_weight=None, eps=1e-5):
+    """The operands of a decode projection, or None unless it runs <= 8 rows against a 2-D weight."""
+    if not all(isinstance(v, TensorProxy) for v in (x, *w, b.output)) or _rows(x) > _GEMV_MAX_ROWS or w[0].ndim != 2:
+        return None
+    return dict(x=x, w=w, bias=bias, residual=residual, act=act, gate=gate, norm=bool(norm), norm_weight=norm_weight,
+                eps=eps, out=b.output, fused=False)
 
-    * the SwiGLU pair ``hip_swiglu(op(x, W1), op(x, W3))`` (or ``mul(silu(a), b)``) -> one gated op;
-    * ``silu(op(...))`` -> ``act="silu"``; ``op(...) + r`` -> the residual epilogue;
-    * ``hip_rms_norm_fwd`` feeding only such ops (rstd unused) -> their norm prologue (one row only:
-      ``_MXFP4_NORM_MAX_ROWS``);
-    * two or three plain siblings of one x (attention q / k / v) -> ``hip_mxfp4_decode_linear_group``
-      (``packed`` when only a trailing ``cat(..., -1)`` reads them).
-    ``LTA_MXFP4_DECODE_FUSION=0`` leaves the custom op in place (A/B)."""
-    import os
 
-    if os.environ.get("LTA_MXFP4_DECODE_FUSION", "1") == "0":
+def _bf16_decode_candidate(b):
+    if b.sym is hip_linear:
+        p = operands(b)
+        return _decode_record(b, p["x"], (p["w"],), p["bias"], p["residual"], p["act"])
+    if b.sym is hip_decode_linear:
+        p = operands(b)
+        gate = None if p["gate_weight"] is None else (p["gate_weight"],)
+        return _decode_record(b, p["x"], (p["w"],), p["bias"], p["residual"], p["act"], gate, p["norm"],
+                              p["norm_weight"], p["eps"])
+    return None
+
+
+def _mxfp4_decode_candidate(b):
+    if b.sym.id not in _MXFP4_LINEAR_IDS:
+        return None
+    p = operands(b, ("x", "q", "s", "bias", "fp4_activations"))
+    x, bias = p["x"], p["bias"]
+    if not isinstance(x, TensorProxy) or x.device.type != "cuda" or x.dtype != torch.bfloat16:
+        return None
+    if any(getattr(v, "requires_grad", False) for v in (x, bias, b.output)):
+        return None  # the op's autograd stays with the custom op
+    return _decode_record(b, x, (p["q"], p["s"]), bias)
+
+
+class _DecodeKind(NamedTuple):
+    """What the decode fusion needs to know about a weight format."""
+    candidate: Callable  # bound symbol -> operand record, or None
+    linear: object  # the operator emitted for one record: (x, *w, bias, residual, act, *gate, norm, norm_weight, eps)
+    group: object  # ... and for 2-3 sibling records: (x, weights, norm, norm_weight, eps[, packed])
+    norm_max_rows: int
+    lower: bool  # emit the records no fold touched as well (else their bound symbol stays)
+    mul: tuple  # the names under which the written-out gate's mul / silu are matched
+    silu: tuple
+    switch: str | None = None  # environment variable that turns the pass off with "0" (A/B)
+
+
+_BF16_DECODE = _DecodeKind(_bf16_decode_candidate, hip_decode_linear, hip_decode_linear_group, _GEMV_MAX_ROWS,
+                           lower=False, mul=("mul",), silu=("silu",))
+_MXFP4_DECODE = _DecodeKind(_mxfp4_decode_candidate, hip_mxfp4_decode_linear, hip_mxfp4_decode_linear_group,
+                            _MXFP4_NORM_MAX_ROWS, lower=True, mul=("mul", "torch_mul"), silu=("silu", "torch_silu"),
+                            switch="LTA_MXFP4_DECODE_FUSION")
+
+
+def _silu_arg(b, names):
+    """``a`` when ``b`` is the out-of-place ``silu(a)`` of a tensor, else None."""
+    if b.sym.name not in names or not b.args or (len(b.args) > 1 and b.args[1] not in (False, None)):
+        return None
+    return b.args[0] if isinstance(b.args[0], TensorProxy) else None
+
+
+def _last_dim_cat_parts(b):
+    """The two or three tensors of a ``cat`` along the last dim, else None."""
+    if b.sym.name not in ("cat", "torch_cat", "cat_prim") or not b.args or not isinstance(b.args[0], (list, tuple)):
+        return None
+    parts = b.args[0]
+    dim = b.args[1] if len(b.args) > 1 else b.kwargs.get("dim", 0)
+    if not 2 <= len(parts) <= 3 or not all(isinstance(p, TensorProxy) for p in parts) or dim not in (-1, parts[0].ndim - 1):
+        return None
+    return parts
+
+
+def _fuse_decode(trace, kind: _DecodeKind, folds, message: str):
+    """Decode projections (<= 8 rows: the weight-streaming GEMVs) with what stands around them folded
+    into the launch.  Every candidate becomes an operand record; a fold moves the record to the position
+    of the consumer it absorbs, and the records are emitted at the end.  ``folds`` names the ones to run:
+
+    * ``gate``: ``hip_swiglu(p(x, W1), p(x, W3))``, or written out ``mul(silu(a), b)`` (HF LlamaMLP), both
+      projections plain and read nowhere else -> one record with ``act="silu"`` and W3 as its gate;
+    * ``act``: ``silu(p(...))`` -> ``act="silu"``; ``residual``: ``p(...) + r`` -> the residual epilogue,
+      emitted where the add was (r exists there);
+    * ``norm``: ``hip_rms_norm_fwd`` of at most ``kind.norm_max_rows`` rows that feeds only records, as
+      their x (rstd unused, literal eps) -> their norm prologue;
+    * ``group``: two or three plain sibling records of one x and norm (attention q / k / v) -> one group
+      launch, ``packed`` when a trailing ``cat(..., -1)`` is their only reader.
+    Every launch removed is ~5 us of a ~1 ms decode step on MI355X (kernel floor + boundary)."""
+    if kind.switch is not None and os.environ.get(kind.switch, "1") == "0":
         return trace
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = list(trace.bound_symbols)
-    cand: dict[int, dict] = {}  # position -> operands of the fused op emitted there
-    for i, b in enumerate(bsyms):
-        if b.sym.id not in _MXFP4_LINEAR_IDS:
-            continue
-        p = dict(zip(("x", "q", "s", "bias", "fp4"), b.args))
-        p.update({k: v for k, v in b.kwargs.items() if k in ("bias",)})
-        x, q, s, bias = p.get("x"), p.get("q"), p.get("s"), p.get("bias")
-        if not all(isinstance(v, TensorProxy) for v in (x, q, s)) or not isinstance(b.output, TensorProxy):
-            continue
-        if x.device.type != "cuda" or x.dtype != torch.bfloat16 or _rows(x) > _GEMV_MAX_ROWS or q.ndim != 2:
-            continue
-        if any(getattr(v, "requires_grad", False) for v in (x, bias, b.output)):
-            continue  # the op's autograd stays with the custom op
-        cand[i] = dict(x=x, q=q, s=s, bias=bias, residual=None, act=None, gate_q=None, gate_s=None, norm=False,
-                       norm_weight=None, eps=1e-5, out=b.output)
+    rw = Rewrite(trace, ex)
+    bsyms = rw.bsyms
+    cand = {i: c for i, b in enumerate(bsyms) if (c := kind.candidate(b)) is not None}
     if not cand:
         return trace
-    drop: set[int] = set()
-    group: dict[int, tuple] = {}  # position -> (members' operands, packed output or None)
-    out_names = {o.name for o in tree_flatten(trace.output)[0] if isinstance(o, TensorProxy)} \
-        if trace.output is not None else set()
+    at = {c["out"].name: i for i, c in cand.items()}  # where the record that makes a value stands now
+    group: dict[int, tuple] = {}  # position -> (member records, packed output or None)
+    n = dict.fromkeys(("gate", "act", "residual", "norm", "group"), 0)
 
-    def operands(k):
-        if k in cand:
-            return [v for v in cand[k].values() if isinstance(v, TensorProxy) and v is not cand[k]["out"]]
-        return bsyms[k].flat_proxy_args
+    def reads(c):
+        return [v.name for v in (c["x"], *c["w"], c["bias"], c["residual"], *(c["gate"] or ()), c["norm_weight"])
+                if isinstance(v, TensorProxy)]
 
-    def count_uses():
-        u = {n: 1 for n in out_names}
-        for k in range(len(bsyms)):
-            if k not in drop:
-                for a in operands(k):
-                    u[a.name] = u.get(a.name, 0) + 1
-        return u
+    def plain(c):
+        return c["gate"] is None and c["bias"] is None and c["residual"] is None and c["act"] is None
 
-    def plain(c, epilogue=True):
-        return c["gate_q"] is None and (not epilogue or (c["bias"] is None and c["residual"] is None and c["act"] is None))
-
-    producer = {c["out"].name: i for i, c in cand.items()}  # outputs of the fused ops, as they move
-    made_by = {o.name: i for i, b in enumerate(bsyms) for o in b.flat_proxy_outs}
-
-    def move(j, i, out, **changes):  # the fused op of position j is emitted at i (a consumer it absorbs)
+    def move(j, i, out, **changes):  # the record of position j is emitted at i (a consumer it absorbs)
         c = cand.pop(j)
-        c.update(changes, out=out)
+        del at[c["out"].name]
+        c.update(changes, out=out, fused=True)
         cand[i] = c
-        drop.add(j)
-        producer.pop(c["out"].name, None)
-        producer[out.name] = i
+        at[out.name] = i
+        rw.drop(j)
 
-    def gate_pair(i, a, g, out, extra=()):
-        ja, jg = producer.get(a.name), producer.get(g.name)
-        if ja is None or jg is None or ja == jg or uses.get(a.name) != 1 or uses.get(g.name) != 1:
+    def gate_pair(i, a, g, out):
+        ja, jg = at.get(a.name), at.get(g.name)
+        if ja is None or jg is None or ja == jg or rw.uses(a) != 1 or rw.uses(g) != 1:
             return False
         ca, cg = cand[ja], cand[jg]
         if ca["x"].name != cg["x"].name or not plain(ca) or not plain(cg) or ca["norm"] or cg["norm"]:
             return False
-        if tuple(ca["q"].shape) != tuple(cg["q"].shape) or out.dtype != a.dtype:
+        if tuple(ca["w"][0].shape) != tuple(cg["w"][0].shape) or out.dtype != a.dtype:
             return False
-        cand.pop(jg)
-        producer.pop(g.name, None)
-        drop.add(jg)
-        drop.update(extra)
-        move(ja, i, out, act="silu", gate_q=cg["q"], gate_s=cg["s"])
+        del cand[jg], at[g.name]
+        rw.drop(jg)
+        move(ja, i, out, act="silu", gate=cg["w"])
+        n["gate"] += 1
         return True
 
-    n_gated = n_act = n_res = n_norm = n_group = 0
-    # SwiGLU pairs: hip_swiglu(a, b), or written out as mul(silu(a), b) (HF LlamaMLP)
-    uses = count_uses()
-    for i, b in enumerate(bsyms):
-        if i in drop or i in cand or len(b.args) != 2 or not all(isinstance(a, TensorProxy) for a in b.args):
-            continue
-        if b.sym is hip_swiglu:
-            n_gated += gate_pair(i, b.args[0], b.args[1], b.output)
-        elif b.sym.name in ("mul", "torch_mul"):
-            for s_arg, g_arg in (b.args, b.args[::-1]):
-                js = made_by.get(s_arg.name)
-                if js is None or js in drop or js in cand or uses.get(s_arg.name) != 1:
-                    continue
-                sb = bsyms[js]
-                if sb.sym.name not in ("silu", "torch_silu") or not sb.args:
-                    continue
-                if len(sb.args) > 1 and sb.args[1] not in (False, None) or not isinstance(sb.args[0], TensorProxy):
-                    continue
-                if gate_pair(i, sb.args[0], g_arg, b.output, extra=(js,)):
-                    n_gated += 1
-                    break
+    def untouched(i):
+        return i not in cand and not rw.dropped(i)
 
-    # linear -> silu
-    uses = count_uses()
-    for i, b in enumerate(bsyms):
-        if i in drop or i in cand or b.sym.name not in ("silu", "torch_silu") or not b.args:
-            continue
-        a = b.args[0]
-        if len(b.args) > 1 and b.args[1] not in (False, None) or not isinstance(a, TensorProxy):
-            continue
-        j = producer.get(a.name)
-        if j is None or uses.get(a.name) != 1 or b.output.dtype != a.dtype:
-            continue
-        c = cand[j]
-        if c["gate_q"] is not None or c["act"] is not None or c["residual"] is not None:
-            continue
-        move(j, i, b.output, act="silu")
-        n_act += 1
-
-    # residual adds
-    uses = count_uses()
-    for i, b in enumerate(bsyms):
-        if i in drop or i in cand or b.sym.name not in ("torch_add", "add") or b.kwargs.get("alpha") not in (None, 1):
-            continue
-        if len(b.args) < 2 or not all(isinstance(a, TensorProxy) for a in b.args[:2]):
-            continue
-        for pos in (0, 1):
-            y, r = b.args[pos], b.args[1 - pos]
-            j = producer.get(y.name)
-            if j is None or uses.get(y.name) != 1 or y.name == r.name:
+    if "gate" in folds:
+        for i, b in enumerate(bsyms):
+            if not untouched(i) or len(b.args) != 2 or not all(isinstance(a, TensorProxy) for a in b.args):
+                continue
+            if b.sym is hip_swiglu:
+                gate_pair(i, b.args[0], b.args[1], b.output)
+            elif b.sym.name in kind.mul:
+                for s_arg, g_arg in (b.args, b.args[::-1]):
+                    js = rw.producer(s_arg)
+                    if js is None or not untouched(js) or rw.uses(s_arg) != 1:
+                        continue
+                    a = _silu_arg(bsyms[js], kind.silu)
+                    if a is not None and gate_pair(i, a, g_arg, b.output):
+                        rw.drop(js)
+                        break
+    if "act" in folds:
+        for i, b in enumerate(bsyms):
+            a = _silu_arg(b, kind.silu) if untouched(i) else None
+            j = at.get(a.name) if a is not None else None
+            if j is None or rw.uses(a) != 1 or b.output.dtype != a.dtype:
                 continue
             c = cand[j]
-            if c["gate_q"] is not None or c["residual"] is not None:
+            if c["gate"] is None and c["act"] is None and c["residual"] is None:
+                move(j, i, b.output, act="silu")
+                n["act"] += 1
+    if "residual" in folds:
+        for i, b in enumerate(bsyms):
+            for y, r in _residual_adds(b) if untouched(i) else ():
+                j = at.get(y.name)
+                if j is None or rw.uses(y) != 1 or y.name == r.name:
+                    continue
+                if cand[j]["gate"] is None and cand[j]["residual"] is None:
+                    move(j, i, b.output, residual=r)
+                    n["residual"] += 1
+                    break
+    if "norm" in folds:
+        for i, b in enumerate(bsyms):
+            if b.sym is not hip_rms_norm_fwd:
                 continue
-            if tuple(r.shape) != tuple(y.shape) or r.dtype != y.dtype or tuple(b.output.shape) != tuple(y.shape):
+            p = operands(b)
+            y, rstd = b.output
+            if rw.uses(rstd) or not isinstance(p["eps"], (int, float)) or _rows(p["x"]) > kind.norm_max_rows:
                 continue
-            move(j, i, b.output, residual=r)  # emitted where the add was: r exists there
-            n_res += 1
-            break
-
-    # RMSNorm prologues
-    uses = count_uses()
-    for i, b in enumerate(bsyms):
-        if i in drop or b.sym is not hip_rms_norm_fwd:
-            continue
-        y, rstd = b.output
-        x, g, eps = b.args[0], b.args[1], b.args[2]
-        if uses.get(rstd.name, 0) or not isinstance(eps, (int, float)) or _rows(x) > _MXFP4_NORM_MAX_ROWS:
-            continue
-        consumers = [k for k in range(len(bsyms)) if k not in drop and any(a.name == y.name for a in operands(k))]
-        ok = bool(consumers) and len(consumers) == uses.get(y.name, 0)
-        for k in consumers:
-            c = cand.get(k)
-            ok = ok and c is not None and not c["norm"] and c["x"].name == y.name and all(
-                getattr(v, "name", None) != y.name for key, v in c.items() if key not in ("x", "out"))
-        if not ok:
-            continue
-        for k in consumers:
-            cand[k].update(x=x, norm=True, norm_weight=g, eps=float(eps))
-        drop.add(i)
-        n_norm += 1
-
-    # sibling projections of one x and norm
-    sibs: dict = {}
-    for i in sorted(cand):
-        c = cand[i]
-        if plain(c):
-            sibs.setdefault((c["x"].name, c["norm"], getattr(c["norm_weight"], "name", None), c["eps"]), []).append(i)
-    uses = count_uses()
-    for ci, cb in enumerate(bsyms):
-        if ci in drop or cb.sym.name not in ("cat", "torch_cat", "cat_prim") or not cb.args \
-                or not isinstance(cb.args[0], (list, tuple)):
-            continue
-        parts = cb.args[0]
-        dim = cb.args[1] if len(cb.args) > 1 else cb.kwargs.get("dim", 0)
-        if not 2 <= len(parts) <= 3 or not all(isinstance(p, TensorProxy) for p in parts) \
-                or dim not in (-1, parts[0].ndim - 1):
-            continue
-        js = [producer.get(p.name) for p in parts]
-        if any(j is None or uses.get(p.name) != 1 for j, p in zip(js, parts)) or len(set(js)) != len(js):
-            continue
-        key = next((k for k, idxs in sibs.items() if js[0] in idxs), None)
-        if key is None or any(j not in sibs[key] for j in js):
-            continue
-        group[ci] = ([cand.pop(j) for j in js], cb.output)
-        drop.update(js)
-        sibs[key] = [j for j in sibs[key] if j not in js]
-        n_group += 1
-    for idxs in sibs.values():
-        for c0 in range(0, len(idxs) - 1, 3):
-            chunk = idxs[c0:c0 + 3]
-            if len(chunk) < 2:
+            if any(untouched(k) for k in rw.consumers(y)):
+                continue  # read by something that is no record
+            readers = [c for c in cand.values() if y.name in reads(c)]
+            if not readers or any(c["norm"] or c["x"].name != y.name or reads(c).count(y.name) != 1 for c in readers):
                 continue
-            group[chunk[0]] = ([cand.pop(j) for j in chunk], None)  # x and the norm weight exist there
-            drop.update(chunk[1:])
-            n_group += 1
-
-    out = []
-    for i, b in enumerate(bsyms):
-        if i in group:
-            members, packed_out = group[i]
-            c = members[0]
-            ws = tuple((m["q"], m["s"]) for m in members)
-            if packed_out is not None:
-                nb = hip_mxfp4_decode_linear_group.bind(c["x"], ws, c["norm"], c["norm_weight"], c["eps"], True,
-                                                        output=packed_out)
-            else:
-                nb = hip_mxfp4_decode_linear_group.bind(c["x"], ws, c["norm"], c["norm_weight"], c["eps"],
-                                                        output=tuple(m["out"] for m in members))
-            out.append(ex.bind_call_ctx(nb))
-        elif i in cand:
+            for c in readers:
+                c.update(x=p["x"], norm=True, norm_weight=p["weight"], eps=float(p["eps"]), fused=True)
+            rw.drop(i)
+            n["norm"] += 1
+    if "group" in folds:
+        sibs: dict = {}  # (x, norm) -> positions of the plain records, in program order
+        for i in sorted(cand):
             c = cand[i]
-            out.append(ex.bind_call_ctx(hip_mxfp4_decode_linear.bind(
-                c["x"], c["q"], c["s"], c["bias"], c["residual"], c["act"], c["gate_q"], c["gate_s"], c["norm"],
-                c["norm_weight"], c["eps"], output=c["out"])))
-        elif i not in drop:
-            out.append(b)
-    new = from_trace(trace)
-    new.bound_symbols = out
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(
-        f"hipex: MXFP4 decode GEMV fusion ({n_gated} gated pair(s), {n_act} activation(s), {n_res} residual(s), "
-        f"{n_norm} norm prologue(s), {n_group} group(s))"))
-    return new
+            if plain(c):
+                sibs.setdefault((c["x"].name, c["norm"], getattr(c["norm_weight"], "name", None), c["eps"]), []).append(i)
+        for ci, cb in enumerate(bsyms):
+            parts = _last_dim_cat_parts(cb) if untouched(ci) else None
+            if parts is None:
+                continue
+            js = [at.get(p.name) for p in parts]
+            if any(j is None or rw.uses(p) != 1 for j, p in zip(js, parts)) or len(set(js)) != len(js):
+                continue
+            key = next((k for k, idxs in sibs.items() if js[0] in idxs), None)
+            if key is None or any(j not in sibs[key] for j in js):
+                continue
+            group[ci] = ([cand.pop(j) for j in js], cb.output)
+            rw.drop(*js)
+            sibs[key] = [j for j in sibs[key] if j not in js]
+        for idxs in sibs.values():
+            for c0 in range(0, len(idxs) - 1, 3):
+                chunk = idxs[c0:c0 + 3]
+                group[chunk[0]] = ([cand.pop(j) for j in chunk], None)  # x and the norm weight exist there
+                rw.drop(*chunk[1:])
+        n["group"] = len(group)
+
+    for i, (members, packed_out) in group.items():
+        c = members[0]
+        ws = tuple(m["w"] if len(m["w"]) > 1 else m["w"][0] for m in members)
+        if packed_out is not None:
+            rw.replace(i, kind.group.bind(c["x"], ws, c["norm"], c["norm_weight"], c["eps"], True, output=packed_out))
+        else:
+            rw.replace(i, kind.group.bind(c["x"], ws, c["norm"], c["norm_weight"], c["eps"],
+                                          output=tuple(m["out"] for m in members)))
+    for i, c in cand.items():
+        if kind.lower or c["fused"]:
+            gate = c["gate"] or (None,) * len(c["w"])
+            rw.replace(i, kind.linear.bind(c["x"], *c["w"], c["bias"], c["residual"], c["act"], *gate, c["norm"],
+                                           c["norm_weight"], c["eps"], output=c["out"]))
+    return rw.finish(message.format(**n))
 
 
 def _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
@@ -1194,58 +936,42 @@ def _fuse_kv_cache_writes(trace):
     vc = index_copy_inplace(cache_v, 2, pos, v)`` (k, v used nowhere else) ->
     ``q, kc, vc = hip_qkv_rope_cache(..., cache_k, cache_v, pos)``: the rotated keys and the values
     are stored straight into the static caches by the RoPE kernel (two launches fewer per layer)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = list(trace.bound_symbols)
-    uses: dict[str, list[int]] = {}
-    for i, b in enumerate(bsyms):
-        for a in b.flat_proxy_args:
-            uses.setdefault(a.name, []).append(i)
-    out_names = {o.name for o in tree_flatten(trace.output)[0] if isinstance(o, TensorProxy)} \
-        if trace.output is not None else set()
-    replace, drop = {}, set()
-    for i, b in enumerate(bsyms):
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
         if b.sym is not hip_qkv_rope:
             continue
         q, k, v = b.output
-        uk, uv = uses.get(k.name, []), uses.get(v.name, [])
-        if len(uk) != 1 or len(uv) != 1 or k.name in out_names or v.name in out_names:
+        if rw.uses(k) != 1 or rw.uses(v) != 1:
             continue
-        ck, cv = bsyms[uk[0]], bsyms[uv[0]]
+        (ik,), (iv,) = rw.consumers(k), rw.consumers(v)
+        ck, cv = rw.bsyms[ik], rw.bsyms[iv]
         if ck.sym.name != "index_copy_inplace" or cv.sym.name != "index_copy_inplace":
             continue
-        (bk, dk, pk, sk), (bv, dv, pv, sv) = ck.args[:4], cv.args[:4]
-        if dk != 2 or dv != 2 or sk is not k or sv is not v or getattr(pk, "name", None) != getattr(pv, "name", 1):
+        wk, wv = operands(ck), operands(cv)
+        if wk["dim"] != 2 or wv["dim"] != 2 or wk["src"] is not k or wv["src"] is not v:
             continue
-        if pk.dtype != torch.int64 or bk.dtype != k.dtype or bv.dtype != v.dtype:
+        bk, bv, pos = wk["buf"], wv["buf"], wk["index"]
+        if getattr(pos, "name", None) != getattr(wv["index"], "name", 1):
             continue
-        nb = ex.bind_call_ctx(hip_qkv_rope_cache.bind(*b.args, bk, bv, pk, output=(q, ck.output, cv.output)))
+        if pos.dtype != torch.int64 or bk.dtype != k.dtype or bv.dtype != v.dtype:
+            continue
         # the fused op needs the caches and positions: emit it where the RoPE was when they exist
         # there (LitGPT), else at the later cache write (HF computes the positions after the RoPE),
         # provided nothing reads q in between
-        producer_pos = {o.name: j for j, bb in enumerate(bsyms) for o in bb.flat_proxy_outs}
-        ready = max([producer_pos.get(x.name, -1) for x in (bk, bv, pk)] + [-1])
-        if ready < i:
-            at = i
-        else:
-            at = max(uk[0], uv[0])
-            if any(i < j < at for j in uses.get(q.name, [])) or ready >= at:
+        ready = max(rw.producer(t, -1) for t in (bk, bv, pos))
+        at = i
+        if ready >= i:
+            at = max(ik, iv)
+            if any(i < j < at for j in rw.consumers(q)) or ready >= at:
                 continue
             # moving the first cache write later: nothing in between may read its result or the
-            # cache it writes (ADVICE r2)
-            lo = min(uk[0], uv[0])
-            watch = {ck.output.name, cv.output.name, bk.name, bv.name}
-            if any(lo < j < at for w in watch for j in uses.get(w, [])):
+            # cache it writes
+            lo = min(ik, iv)
+            if any(lo < j < at for t in (ck.output, cv.output, bk, bv) for j in rw.consumers(t)):
                 continue
-        replace[at] = nb
-        drop.update({i, uk[0], uv[0]} - {at})
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} KV-cache write pair(s) fused into RoPE"))
-    return new
+        rw.replace(at, hip_qkv_rope_cache.bind(*b.args, bk, bv, pos, output=(q, ck.output, cv.output)))
+        rw.drop(*({i, ik, iv} - {at}))
+    return rw.finish(f"hipex: {rw.replaced} KV-cache write pair(s) fused into RoPE")
 
 
 def _fuse_rms_bwd_residual(trace):
@@ -1253,54 +979,23 @@ def _fuse_rms_bwd_residual(trace):
     ``(z, dw) = hip_rms_norm_bwd(g, x, w, rstd, r)``: the residual stream's gradient is added in the
     normalisation backward's store pass instead of a separate elementwise launch.  The same for
     ``hip_layer_norm_bwd`` (GPT-2 / NeoX blocks)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = trace.bound_symbols
-    uses: dict[str, int] = {}
-    for b in bsyms:
-        for a in b.flat_proxy_args:
-            uses[a.name] = uses.get(a.name, 0) + 1
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym.name not in ("torch_add", "add") or b.kwargs.get("alpha") not in (None, 1):
-            continue
-        if len(b.args) < 2 or not all(isinstance(a, TensorProxy) for a in b.args[:2]):
-            continue
-        for pos in (0, 1):
-            y, r = b.args[pos], b.args[1 - pos]
-            j = producer.get(y.name)
-            if j is None or j in drop or j in replace or uses.get(y.name, 0) != 1:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        for y, r in _residual_adds(b):
+            j = rw.producer(y)
+            if j is None or rw.touched(j) or rw.uses(y) != 1:
                 continue
-            rb = bsyms[j]
-            if rb.sym is hip_rms_norm_bwd:
-                nargs = 4  # (dy, x, weight, rstd[, residual])
-            elif rb.sym is hip_layer_norm_bwd:
-                nargs = 6  # (dy, x, weight, mean, rstd, has_bias[, residual])
-            else:
+            rb = rw.bsyms[j]
+            if rb.sym is not hip_rms_norm_bwd and rb.sym is not hip_layer_norm_bwd:
                 continue
-            if len(rb.args) > nargs and rb.args[nargs] is not None:
+            p = operands(rb)
+            if p["residual"] is not None or rb.output[0] is not y or b.output.dtype != y.dtype or rw.producer(r, -1) > j:
                 continue
-            outs = rb.output
-            if outs[0] is not y or tuple(r.shape) != tuple(y.shape) or r.dtype != y.dtype:
-                continue
-            if tuple(b.output.shape) != tuple(y.shape) or b.output.dtype != y.dtype or producer.get(r.name, -1) > j:
-                continue
-            nb = ex.bind_call_ctx(rb.sym.bind(*rb.args[:nargs], r, output=(b.output, *outs[1:])))
-            replace[j] = nb
-            drop.add(i)
+            p["residual"] = r  # the last parameter of both
+            rw.replace(j, rb.sym.bind(*p.values(), output=(b.output, *rb.output[1:])))
+            rw.drop(i)
             break
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} residual-gradient add(s) fused into a normalisation backward"))
-    return new
+    return rw.finish(f"hipex: {rw.replaced} residual-gradient add(s) fused into a normalisation backward")
 
 
 # ---- fused SwiGLU GEMMs (csrc/gemm4.hip EPI 1 / 2) ---------------------------------------
@@ -1336,9 +1031,17 @@ hip_matmul_swiglu_bwd = ex.register_operator(
     "hip_matmul_swiglu_bwd", meta=lambda dy, w, a, b: (TensorProxy(like=a), TensorProxy(like=b)), fn=_mm_swiglu_bwd_impl)
 
 
+def _plain_linear(b):
+    """The operands of ``b`` when it is a ``hip_linear`` without bias, residual or activation, else None."""
+    if b.sym is not hip_linear:
+        return None
+    p = operands(b)
+    return p if p["bias"] is None and p["residual"] is None and p["act"] is None else None
+
+
 def _fuse_swiglu_gemms(trace):
     """LLaMA-MLP SwiGLU chains onto the GEMM epilogues (prefill / training shapes; decode rows go to
-    the gated GEMV of :func:`_fuse_decode_gemv`):
+    the gated GEMV of :func:`_fuse_decode`):
 
     * forward: ``a = hip_linear(x, w1); b = hip_linear(x, w2); y = hip_swiglu(a, b)`` ->
       ``a, b, y = hip_gate_up(x, w1, w2)`` (one launch; ``hip_gate_up_y`` when nothing else reads
@@ -1347,72 +1050,49 @@ def _fuse_swiglu_gemms(trace):
       ``da, db = hip_matmul_swiglu_bwd(dy, w, a, b)``.
     Reference counterpart: nvFuser fusing the pointwise SwiGLU into its matmul segments
     (thunder/executors/nvfuserex_impl.py:2437-2488)."""
-    from ..core.trace import from_trace, TraceProvenance
     from ..ops.gemm import _fused_swiglu_on
 
     if not _fused_swiglu_on():
         return trace
-    bsyms = list(trace.bound_symbols)
-    uses: dict[str, list] = {}
-    for k, b in enumerate(bsyms):
-        for a in b.flat_proxy_args:
-            uses.setdefault(a.name, []).append(k)
-    outs = {o.name for o in tree_flatten(trace.output)[0] if isinstance(o, TensorProxy)} if trace.output is not None else set()
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
+    rw = Rewrite(trace, ex)
     n_fwd = n_bwd = 0
-    for i, b in enumerate(bsyms):
-        if b.sym is hip_swiglu and len(b.args) == 2:
-            a, g = b.args
-            ja, jg = producer.get(a.name), producer.get(g.name)
-            if ja is None or jg is None or ja == jg or {ja, jg} & (drop | set(replace)):
+    for i, b in enumerate(rw.bsyms):
+        if b.sym is hip_swiglu:
+            a, g = operands(b).values()
+            ja, jg = rw.producer(a), rw.producer(g)
+            if ja is None or jg is None or ja == jg or rw.touched(ja) or rw.touched(jg):
                 continue
-            la, lg = bsyms[ja], bsyms[jg]
-            if la.sym is not hip_linear or lg.sym is not hip_linear:
-                continue
-            pa, pg = _linear_parts(la), _linear_parts(lg)
-            if pa["x"].name != pg["x"].name or any(p.get(k) is not None for p in (pa, pg) for k in ("bias", "residual", "act")):
+            pa, pg = _plain_linear(rw.bsyms[ja]), _plain_linear(rw.bsyms[jg])
+            if pa is None or pg is None or pa["x"].name != pg["x"].name:
                 continue
             x, w1, w2 = pa["x"], pa["w"], pg["w"]
             if tuple(w1.shape) != tuple(w2.shape) or _rows(x) <= _GEMV_MAX_ROWS or x.dtype != torch.bfloat16:
                 continue
             at = max(ja, jg)
-            # every other reader of a / b must come after the fused op's position
-            others = [k for k in uses.get(a.name, []) + uses.get(g.name, []) if k != i]
+            # every other reader of a / b (the return included) must come after the fused op's position
+            others = [k for k in rw.consumers(a) + rw.consumers(g) if k != i]
             if any(k <= at for k in others):
                 continue
-            if others or a.name in outs or g.name in outs:
-                nb = ex.bind_call_ctx(hip_gate_up.bind(x, w1, w2, output=(a, g, b.output)))
+            if others:
+                rw.replace(at, hip_gate_up.bind(x, w1, w2, output=(a, g, b.output)))
             else:
-                nb = ex.bind_call_ctx(hip_gate_up_y.bind(x, w1, w2, output=b.output))
-            replace[at] = nb
-            drop.update((min(ja, jg), i))
+                rw.replace(at, hip_gate_up_y.bind(x, w1, w2, output=b.output))
+            rw.drop(min(ja, jg), i)
             n_fwd += 1
-        elif b.sym is hip_swiglu_bwd and len(b.args) == 3:
-            g, a, bb = b.args
-            j = producer.get(g.name)
-            if j is None or j in drop or j in replace or bsyms[j].sym is not hip_matmul:
+        elif b.sym is hip_swiglu_bwd:
+            g, a, bb = operands(b).values()
+            j = rw.producer(g)
+            if j is None or rw.touched(j) or rw.bsyms[j].sym is not hip_matmul:
                 continue
-            mb = bsyms[j]
-            if (len(mb.args) > 2 and mb.args[2] is not None) or uses.get(g.name, []) != [i] or g.name in outs:
+            m = operands(rw.bsyms[j])
+            if m["residual"] is not None or rw.consumers(g) != [i]:
                 continue
-            dy, w = mb.args[0], mb.args[1]
-            if w.ndim != 2 or tuple(a.shape) != tuple(g.shape) or tuple(bb.shape) != tuple(g.shape):
+            if m["b"].ndim != 2 or tuple(a.shape) != tuple(g.shape) or tuple(bb.shape) != tuple(g.shape):
                 continue
-            replace[i] = ex.bind_call_ctx(hip_matmul_swiglu_bwd.bind(dy, w, a, bb, output=b.output))
-            drop.add(j)
+            rw.replace(i, hip_matmul_swiglu_bwd.bind(m["a"], m["b"], a, bb, output=b.output))
+            rw.drop(j)
             n_bwd += 1
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {n_fwd} gate-up SwiGLU GEMM(s), {n_bwd} SwiGLU-backward GEMM epilogue(s)"))
-    return new
+    return rw.finish(f"hipex: {n_fwd} gate-up SwiGLU GEMM(s), {n_bwd} SwiGLU-backward GEMM epilogue(s)")
 
 
 def _linear_qkv_rope_impl(x, w, cos, sin, n_head, n_query_groups, head_size, rope_n):
@@ -1431,6 +1111,22 @@ def _linear_qkv_rope_meta(x, w, cos, sin, n_head, n_query_groups, head_size, rop
 hip_linear_qkv_rope = ex.register_operator("hip_linear_qkv_rope", meta=_linear_qkv_rope_meta, fn=_linear_qkv_rope_impl)
 
 
+def _rope_of_gemm(rw, i, b, gemm):
+    """``(j, rope operands)`` when ``b`` (at i) is the ``hip_qkv_rope`` of a ``gemm`` output at j that nothing
+    else reads, with literal head geometry and cos / sin that exist where the GEMM runs; else None."""
+    if b.sym is not hip_qkv_rope:
+        return None
+    r = operands(b)
+    j = rw.producer(r["qkv"])
+    if j is None or rw.touched(j) or rw.bsyms[j].sym is not gemm or rw.consumers(r["qkv"]) != [i]:
+        return None
+    if not all(isinstance(r[k], int) for k in ("n_head", "n_query_groups", "head_size", "rope_n")):
+        return None
+    if rw.producer(r["cos"], -1) > j or rw.producer(r["sin"], -1) > j:
+        return None
+    return j, r
+
+
 def _fuse_qkv_rope_gemm(trace):
     """``qkv = hip_linear(x, w); q, k, v = hip_qkv_rope(qkv, cos, sin, ...)`` (qkv read nowhere else,
     prefill / training rows) -> ``q, k, v = hip_linear_qkv_rope(x, w, cos, sin, ...)``: the attention
@@ -1438,43 +1134,19 @@ def _fuse_qkv_rope_gemm(trace):
     [B, T, (nh + 2 ng) D] projection output never goes to HBM.  Reference counterpart: the
     torch.compile / nvFuser cat+RoPE fusion of thunder/executors/torch_compile.py (rope) — here it
     lands in the GEMM itself."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = list(trace.bound_symbols)
-    uses: dict[str, list] = {}
-    for k, b in enumerate(bsyms):
-        for a in b.flat_proxy_args:
-            uses.setdefault(a.name, []).append(k)
-    outs = {o.name for o in tree_flatten(trace.output)[0] if isinstance(o, TensorProxy)} if trace.output is not None else set()
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_qkv_rope or len(b.args) != 7:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        m = _rope_of_gemm(rw, i, b, hip_linear)
+        if m is None:
             continue
-        qkv, cos, sin, nh, ng, hs, rn = b.args
-        j = producer.get(getattr(qkv, "name", None))
-        if j is None or j in drop or bsyms[j].sym is not hip_linear or uses.get(qkv.name, []) != [i] or qkv.name in outs:
+        j, r = m
+        p = _plain_linear(rw.bsyms[j])
+        if p is None or p["x"].ndim != 3 or _rows(p["x"]) <= _GEMV_MAX_ROWS:
             continue
-        p = _linear_parts(bsyms[j])
-        if any(p.get(k) is not None for k in ("bias", "residual", "act")) or p["x"].ndim != 3 or _rows(p["x"]) <= _GEMV_MAX_ROWS:
-            continue
-        if not all(isinstance(v, int) for v in (nh, ng, hs, rn)):
-            continue
-        if producer.get(getattr(cos, "name", None), -1) > j or producer.get(getattr(sin, "name", None), -1) > j:
-            continue  # cos / sin must exist where the GEMM runs
-        replace[j] = ex.bind_call_ctx(hip_linear_qkv_rope.bind(p["x"], p["w"], cos, sin, nh, ng, hs, rn, output=b.output))
-        drop.add(i)
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} qkv projection(s) with the RoPE split in the GEMM epilogue"))
-    return new
+        rw.replace(j, hip_linear_qkv_rope.bind(p["x"], p["w"], r["cos"], r["sin"], r["n_head"], r["n_query_groups"],
+                                               r["head_size"], r["rope_n"], output=b.output))
+        rw.drop(i)
+    return rw.finish(f"hipex: {rw.replaced} qkv projection(s) with the RoPE split in the GEMM epilogue")
 
 
 def _fp8_gemm_qkv_rope_impl(qa, qb, sa, sb, out_shape, cos, sin, n_head, n_query_groups, head_size, rope_n):
@@ -1498,46 +1170,23 @@ def _fuse_fp8_qkv_rope_gemm(trace):
     read nowhere else) -> ``q, k, v = hip_fp8_gemm_qkv_rope(...)``: the FP8 path's counterpart of
     :func:`_fuse_qkv_rope_gemm` (csrc/gemm4_fp8.hip QKV epilogue; reference: TransformerEngine's fused
     attention input projection, thunder/executors/transformer_engineex_impl.py)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = list(trace.bound_symbols)
-    uses: dict[str, list] = {}
-    for k, b in enumerate(bsyms):
-        for a in b.flat_proxy_args:
-            uses.setdefault(a.name, []).append(k)
-    outs = {o.name for o in tree_flatten(trace.output)[0] if isinstance(o, TensorProxy)} if trace.output is not None else set()
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_qkv_rope or len(b.args) != 7:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        m = _rope_of_gemm(rw, i, b, hip_fp8_gemm)
+        if m is None:
             continue
-        qkv, cos, sin, nh, ng, hs, rn = b.args
-        j = producer.get(getattr(qkv, "name", None))
-        if j is None or j in drop or j in replace or bsyms[j].sym is not hip_fp8_gemm or uses.get(qkv.name, []) != [i] \
-                or qkv.name in outs:
+        j, r = m
+        g = operands(rw.bsyms[j])
+        if g["out_shape"] is None or g["residual"] is not None or g["fmt_a"] != 0 or g["fmt_b"] != 0 or g["bias"] is not None:
             continue
-        ga = bsyms[j].args
-        if len(ga) < 8 or (len(ga) > 8 and ga[8] is not None) or ga[4] != 0 or ga[5] != 0 or ga[6] is not None:
+        out_shape = tuple(g["out_shape"])
+        if len(out_shape) != 3 or not all(isinstance(v, int) for v in out_shape):
             continue
-        out_shape = tuple(ga[7])
-        if len(out_shape) != 3 or not all(isinstance(v, int) for v in (nh, ng, hs, rn) + out_shape):
-            continue
-        if producer.get(getattr(cos, "name", None), -1) > j or producer.get(getattr(sin, "name", None), -1) > j:
-            continue
-        replace[j] = ex.bind_call_ctx(hip_fp8_gemm_qkv_rope.bind(ga[0], ga[1], ga[2], ga[3], out_shape, cos, sin, nh, ng,
-                                                                 hs, rn, output=b.output))
-        drop.add(i)
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} fp8 qkv projection(s) with the RoPE split in the GEMM epilogue"))
-    return new
+        rw.replace(j, hip_fp8_gemm_qkv_rope.bind(g["qa"], g["qb"], g["sa"], g["sb"], out_shape, r["cos"], r["sin"],
+                                                 r["n_head"], r["n_query_groups"], r["head_size"], r["rope_n"],
+                                                 output=b.output))
+        rw.drop(i)
+    return rw.finish(f"hipex: {rw.replaced} fp8 qkv projection(s) with the RoPE split in the GEMM epilogue")
 
 
 def _attn_bwd_rope_meta(g, q, k, v, o, lse, causal, scale, cos, sin, n_head, n_query_groups):
@@ -1560,46 +1209,29 @@ def _fuse_attn_bwd_rope(trace):
     ``dqkv = hip_flash_attn_bwd_rope(..., cos, sin, n_head, n_query_groups)``: the RoPE backward
     runs in the attention backward's dQ / dK epilogues and the three gradients are stored straight
     into the fused projection's gradient (the mirror of the qkv-RoPE GEMM epilogue of the forward)."""
-    from ..core.trace import from_trace, TraceProvenance
-
-    bsyms = trace.bound_symbols
-    uses: dict[str, int] = {}
-    for b in bsyms:
-        for a in b.flat_proxy_args:
-            uses[a.name] = uses.get(a.name, 0) + 1
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_qkv_rope_bwd or len(b.args) != 9:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        if b.sym is not hip_qkv_rope_bwd:
             continue
-        gq, gk, gv, cos, sin, nh, ng, hs, rn = b.args
-        if not all(isinstance(t, TensorProxy) for t in (gq, gk, gv, cos, sin)) or hs != 128 or rn != hs:
+        r = operands(b)
+        grads = (r["dq"], r["dk"], r["dv"])
+        if not all(isinstance(t, TensorProxy) for t in (*grads, r["cos"], r["sin"])):
             continue
-        j = producer.get(gq.name)
-        if j is None or j in drop or bsyms[j].sym is not hip_attn_bwd:
+        if r["head_size"] != 128 or r["rope_n"] != r["head_size"]:
             continue
-        ab = bsyms[j]
-        if tuple(o.name for o in ab.flat_proxy_outs) != (gq.name, gk.name, gv.name):
+        j = rw.producer(grads[0])
+        if j is None or rw.touched(j) or rw.bsyms[j].sym is not hip_attn_bwd:
             continue
-        if any(uses.get(t.name, 0) != 1 for t in (gq, gk, gv)):
+        ab = rw.bsyms[j]
+        if tuple(o.name for o in ab.flat_proxy_outs) != tuple(t.name for t in grads) or any(rw.uses(t) != 1 for t in grads):
             continue
-        g, q, k, v, o, lse, causal, scale = ab.args
-        if q.shape[1] != nh or k.shape[1] != ng or q.shape[2] != k.shape[2]:
+        a = operands(ab)
+        nh, ng = r["n_head"], r["n_query_groups"]
+        if a["q"].shape[1] != nh or a["k"].shape[1] != ng or a["q"].shape[2] != a["k"].shape[2]:
             continue
-        replace[i] = ex.bind_call_ctx(hip_attn_bwd_rope.bind(g, q, k, v, o, lse, causal, scale, cos, sin, nh, ng,
-                                                             output=b.output))
-        drop.add(j)
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} RoPE backward(s) fused into the attention backward"))
-    return new
+        rw.replace(i, hip_attn_bwd_rope.bind(*a.values(), r["cos"], r["sin"], nh, ng, output=b.output))
+        rw.drop(j)
+    return rw.finish(f"hipex: {rw.replaced} RoPE backward(s) fused into the attention backward")
 
 
 def _rms_bwd_fp8_meta(dy, x, weight, rstd, residual, key, slot):
@@ -1623,41 +1255,21 @@ def _fuse_fp8_rms_bwd_casts(trace):
     norm_2's backward, the previous block's MLP projection after norm_1's), so its e5m2 copy leaves the
     norm backward's store pass (dx keeps its other uses; the cast launch re-reading dx disappears).
     Runs after :func:`_fuse_rms_bwd_residual`, so the residual add is already in the norm backward."""
-    import os
-
-    from ..core.trace import from_trace, TraceProvenance
-
-    if os.environ.get("LTA_FP8_FUSE_PRODUCERS", "1") == "0":  # A/B hook (with the forward producers)
+    if _fp8_producer_fusion_off():
         return trace
-    bsyms = trace.bound_symbols
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_fp8_cast_delayed or len(b.args) != 4 or not b.args[1]:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        c = _delayed_cast(b, e5m2=True)
+        j = rw.producer(c["t"]) if c is not None else None
+        if j is None or rw.touched(j):
             continue
-        y, _, key, slot = b.args
-        j = producer.get(y.name)
-        if j is None or j in replace:
+        pb = rw.bsyms[j]
+        if pb.sym is not hip_rms_norm_bwd or pb.output[0].name != c["t"].name:
             continue
-        pb = bsyms[j]
-        if pb.sym is not hip_rms_norm_bwd or pb.output[0].name != y.name:
-            continue
-        res = pb.args[4] if len(pb.args) > 4 else None
-        nb = hip_rms_norm_bwd_fp8.bind(*pb.args[:4], res, key, slot,
-                                       output=(pb.output[0], pb.output[1], b.output[0], b.output[1]))
-        replace[j] = ex.bind_call_ctx(nb)
-        drop.add(i)
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} e5m2 gradient cast(s) fused into RMSNorm backwards"))
-    return new
+        rw.replace(j, hip_rms_norm_bwd_fp8.bind(*operands(pb).values(), c["key"], c["slot"],
+                                                output=(*pb.output[:2], *b.output)))
+        rw.drop(i)
+    return rw.finish(f"hipex: {rw.replaced} e5m2 gradient cast(s) fused into RMSNorm backwards")
 
 
 def _attn_fwd_fp8_meta(q, k, v, causal, scale, key, slot):
@@ -1715,55 +1327,50 @@ def _fuse_fp8_attn_out_casts(trace):
     v, ..., key, slot)``: the e4m3 input of the FP8 output projection leaves the attention epilogue
     (O is stored [B, T, H, D], so its rows are the projection's rows); O itself is still written for the
     backward.  The view chain stays for its other readers."""
-    import os
-
-    from ..core.trace import from_trace, TraceProvenance
-
-    if os.environ.get("LTA_FP8_FUSE_PRODUCERS", "1") == "0":
+    if _fp8_producer_fusion_off():
         return trace
-    bsyms = trace.bound_symbols
-    producer = {}
-    for i, b in enumerate(bsyms):
-        for o in b.flat_proxy_outs:
-            producer[o.name] = i
-    drop: set[int] = set()
-    replace: dict[int, object] = {}
-    for i, b in enumerate(bsyms):
-        if b.sym is not hip_fp8_cast_delayed or len(b.args) != 4 or b.args[1]:
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        c = _delayed_cast(b, e5m2=False)
+        if c is None:
             continue
-        y, _, key, slot = b.args
-        chain, cur = [], y
-        j = producer.get(cur.name)
-        while j is not None and bsyms[j].sym.name in _HEAD_MERGE_VIEWS and len(chain) < 4:
-            chain.append(bsyms[j])
-            cur = bsyms[j].args[0]
-            if not isinstance(cur, TensorProxy):
-                break
-            j = producer.get(cur.name)
-        if j is None or j in replace or not chain or bsyms[j].sym is not hip_attn_fwd:
+        chain, cur = [], c["t"]
+        j = rw.producer(cur)
+        while j is not None and rw.bsyms[j].sym.name in _HEAD_MERGE_VIEWS and len(chain) < 4:
+            chain.append(rw.bsyms[j])
+            cur = rw.bsyms[j].args[0]
+            j = rw.producer(cur)
+        if j is None or rw.touched(j) or not chain or rw.bsyms[j].sym is not hip_attn_fwd:
             continue
-        ab = bsyms[j]
+        ab = rw.bsyms[j]
         out = ab.output[0]
         if cur.name != out.name or out.dtype != torch.bfloat16 or out.shape[-1] != 128:
             continue
         if not _merges_heads(chain[::-1], out):
             continue
-        nb = hip_attn_fwd_fp8.bind(*ab.args[:5], key, slot, output=(ab.output[0], ab.output[1], b.output[0], b.output[1]))
-        replace[j] = ex.bind_call_ctx(nb)
-        drop.add(i)
-    if not replace:
-        return trace
-    new = from_trace(trace)
-    new.bound_symbols = [replace.get(i, b) for i, b in enumerate(bsyms) if i not in drop]
-    new.scopes = [new.bound_symbols]
-    new.set_provenance(TraceProvenance(f"hipex: {len(replace)} e4m3 attention-output cast(s) fused into the attention epilogue"))
-    return new
+        rw.replace(j, hip_attn_fwd_fp8.bind(*operands(ab).values(), c["key"], c["slot"], output=(*ab.output[:2], *b.output)))
+        rw.drop(i)
+    return rw.finish(f"hipex: {rw.replaced} e4m3 attention-output cast(s) fused into the attention epilogue")
+
+
+_PASSES = (
+    _fuse_fp8_cast_producers, _fuse_fp8_attn_out_casts, _fuse_linear_epilogues, _fuse_rms_bwd_residual,
+    _fuse_fp8_rms_bwd_casts,
+    partial(_fuse_decode, kind=_BF16_DECODE, folds=("gate", "norm"),
+            message="hipex: decode GEMV fusion ({gate} gated pair(s), {norm} norm prologue(s))"),
+    partial(_fuse_decode, kind=_MXFP4_DECODE, folds=("gate", "act", "residual", "norm", "group"),
+            message="hipex: MXFP4 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
+                    "{norm} norm prologue(s), {group} group(s))"),
+    _fuse_swiglu_gemms, _fuse_kv_cache_writes,
+    partial(_fuse_decode, kind=_BF16_DECODE, folds=("group",), message="hipex: {group} grouped decode projection launch(es)"),
+    _fuse_qkv_rope_gemm, _fuse_fp8_qkv_rope_gemm, _fuse_attn_bwd_rope,
+)
 
 
 def _post_claim(trace):
-    return _fuse_attn_bwd_rope(_fuse_fp8_qkv_rope_gemm(_fuse_qkv_rope_gemm(_group_decode_projections(_fuse_kv_cache_writes(_fuse_swiglu_gemms(
-        _fuse_mxfp4_decode(_fuse_decode_gemv(_fuse_fp8_rms_bwd_casts(_fuse_rms_bwd_residual(_fuse_linear_epilogues(
-            _fuse_fp8_attn_out_casts(_fuse_fp8_cast_producers(trace)))))))))))))
+    for rewrite in _PASSES:
+        trace = rewrite(trace)
+    return trace
 
 
 ex.post_claim_pass = _post_claim

@@ -9,7 +9,7 @@ E8M0 scale per 32 input features; ``ops/mxfp4.py``).  At run time:
   the 4-bit weight (once per 8 rows) and multiplies bf16 activations — a quarter of the bf16
   weight bytes per token; in a compiled program with up to 8 rows the HIP executor rewrites the op
   into ``hip_mxfp4_decode_linear`` with the surrounding norm / SwiGLU / residual folded into the
-  launch (``executors/hipex.py`` ``_fuse_mxfp4_decode``);
+  launch (``executors/hipex.py`` ``_fuse_decode``);
 * prefill, ``activations="bf16"`` (default, W4A16): the weight is dequantized to bf16 and the
   product runs on the bf16 GEMM path;
 * prefill, ``activations="mxfp4"`` (W4A4): the activation is MXFP4-quantized as well and the
