@@ -51,6 +51,8 @@ hip_linear = ex.register_operator("hip_linear", meta=_linear_meta, fn=_linear_im
 
 
 def _linear_checker(a, w, bias=None):
+    from ..ops.gemm import _hand_gemm_shape
+
     if not _gpu(a, w, bias) or a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or w.ndim != 2:
         return False
     if bias is not None and (bias.dtype != torch.bfloat16 or bias.ndim != 1):
@@ -66,14 +68,6 @@ def _linear_checker(a, w, bias=None):
     if M <= 8:  # decode: the weight-streaming GEMV (csrc/gemv.hip)
         return K % 8 == 0
     return _hand_gemm_shape(M, N, K)
-
-
-def _hand_gemm_shape(M: int, N: int, K: int) -> bool:
-    """A shape some hand GEMM tiles: gemm4 (any M >= 64 and N % 8 with edge tiles, K % 128) or the
-    8-wave kernel (M, N % 256, K % 64)."""
-    from ..ops.gemm import GEMM4_MIN_M
-
-    return (M >= GEMM4_MIN_M and N % 8 == 0 and K % 128 == 0) or (M % 256 == 0 and N % 256 == 0 and K % 64 == 0)
 
 
 def _linear_exec(a, w, bias=None):
@@ -98,6 +92,8 @@ def _mm_impl(a, b, residual=None):
 
 
 def _mm_checker(a, b):
+    from ..ops.gemm import _hand_gemm_shape
+
     if not _gpu(a, b) or a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or b.ndim != 2 or a.ndim < 2:
         return False
     M = 1

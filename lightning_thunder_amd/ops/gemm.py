@@ -1,7 +1,11 @@
-"""Python bindings of the hand-written CDNA4 GEMMs (``csrc/gemm.hip``, K2)."""
+"""Python bindings of the hand-written CDNA4 GEMMs and the static rule that picks one per call:
+``csrc/gemm4.hip`` (the 4-wave 256 x 256 kernel, every training layout, split-K and wave-tail split, the
+grouped, SwiGLU and qkv-RoPE forms), ``csrc/gemm.hip`` (K2, the 8-wave kernel for tile-divisible shapes
+with K % 64) and ``csrc/gemv.hip`` (decode rows)."""
 from __future__ import annotations
 
 import os as _os
+from typing import NamedTuple
 
 import torch
 
@@ -12,24 +16,51 @@ from ._lib import require, stream_ptr, check, register_signature, dcode, c_int, 
 
 ACT = {None: 0, "none": 0, "gelu_tanh": 1, "gelu": 2, "gelu_erf": 2, "silu": 3, "relu": 4}
 TILE_M, TILE_N, TILE_K = 256, 256, 64
+GEMM4_MIN_M = 64
 
-register_signature("lta_gemm_nt_bf16", [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                        c_int, c_int, c_int, c_float, c_int, c_void_p])
 register_signature("lta_gemm_nt_bf16_v", [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                           c_int, c_int, c_int, c_float, c_int, c_int, c_void_p])
+
+
+def _gemm4_shape(M: int, N: int, K: int) -> bool:
+    """gemm4 tiles any M >= 64 and N % 8 (edge tiles), K % 128."""
+    return M >= GEMM4_MIN_M and N % 8 == 0 and K % 128 == 0
+
+
+def _gemm8_shape(M: int, N: int, K: int) -> bool:
+    """The 8-wave kernel takes whole 256 x 256 x 64 tiles."""
+    return M % TILE_M == 0 and N % TILE_N == 0 and K % TILE_K == 0
+
+
+def _hand_gemm_shape(M: int, N: int, K: int) -> bool:
+    """A shape some hand GEMM tiles (what the executor claims; the operands' layout is checked per call)."""
+    return _gemm4_shape(M, N, K) or _gemm8_shape(M, N, K)
 
 
 def _rowmajor_2d(t: torch.Tensor) -> bool:
     return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
 
 
+def _plain_2d(t: torch.Tensor) -> bool:
+    return t.dtype == torch.bfloat16 and t.is_cuda and _rowmajor_2d(t)
+
+
+def _residual_ok(r, shape=None, rows16: bool = True) -> bool:
+    """A residual the epilogues read: bf16 with unit-stride columns, of ``shape`` when one is given (the
+    matmul rule leaves the shape to the gemm4 / 8-wave entry's assert) and with 16-byte aligned rows
+    unless ``rows16`` is off (matmul4 / matmul_hip called directly take any row pitch)."""
+    if r is None:
+        return True
+    if r.dtype != torch.bfloat16 or (shape is not None and tuple(r.shape) != shape):
+        return False
+    return _rowmajor_2d(r) if rows16 else r.stride(1) == 1
+
+
 def gemm_nt_supported(a: torch.Tensor, b: torch.Tensor, bias=None, residual=None) -> bool:
     """a [M,K] and b [N,K] bf16 on the GPU with tile-divisible shapes (the 8-wave kernel)."""
     if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or not a.is_cuda:
         return False
-    M, K = a.shape
-    N = b.shape[0]
-    if M % TILE_M or N % TILE_N or K % TILE_K:
+    if not _gemm8_shape(a.shape[0], b.shape[0], a.shape[1]):
         return False
     return nt_epilogue_ok(a, b, bias, residual)
 
@@ -47,10 +78,7 @@ def nt_epilogue_ok(a: torch.Tensor, b: torch.Tensor, bias=None, residual=None) -
     if bias is not None and (bias.dtype != torch.bfloat16 or bias.numel() != N or not bias.is_contiguous()
                              or bias.data_ptr() % 16):
         return False
-    if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != (M, N)
-                                 or not _rowmajor_2d(residual)):
-        return False
-    return True
+    return _residual_ok(residual, (M, N))
 
 
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, act=None, alpha: float = 1.0,
@@ -104,15 +132,14 @@ def _device_cus(device) -> int:
     return _CUS[idx]
 
 
-def _tail_workspace(M: int, N: int, K: int, device):
+def tail_tiles(M: int, N: int, K: int, cus: int) -> int:
+    """Tiles of a plain product's last partial wave that run as two K halves (0: no split): more than
+    one wave of tiles, the last one at most half full."""
     if not _TAIL_SPLIT or K % 256:
-        return None
-    cus = _device_cus(device)
+        return 0
     nwg = -(-M // 256) * -(-N // 256)
     tail = nwg % cus
-    if nwg <= cus or tail == 0 or 2 * tail > cus:
-        return None
-    return _workspace(2 * tail * 256 * 256, device)
+    return 0 if nwg <= cus or 2 * tail > cus else tail
 
 
 # under-filled grids of plain products (at most half a wave of 256 x 256 tiles: the wgrad / dgrad of
@@ -159,10 +186,6 @@ def _workspace(need: int, device):
     return ws
 
 
-GEMM4_MIN_M = 64
-_FWD_LIB = _os.environ.get("LTA_GEMM_FWD_LIB", "0") == "1"
-
-
 def gemm4_layout(a: torch.Tensor, b: torch.Tensor):
     """(at, bt, lda, ldb) of ``a [M,K] @ b [K,N]`` for ``lta_gemm4_bf16``, or None when the operands
     are not bf16 2-D GPU tensors with one unit-stride dim and 16-B aligned rows, or K % 128 != 0.
@@ -173,7 +196,7 @@ def gemm4_layout(a: torch.Tensor, b: torch.Tensor):
         return None
     M, K = a.shape
     N = b.shape[1]
-    if b.shape[0] != K or M < GEMM4_MIN_M or N % 8 or K % 128 or N == 0 or K == 0:
+    if b.shape[0] != K or not _gemm4_shape(M, N, K) or N == 0 or K == 0:
         return None
     la, lb = _operand_layout(a, M, K), _operand_layout(b, K, N)
     if la is None or lb is None:
@@ -196,44 +219,12 @@ def matmul4(a: torch.Tensor, b: torch.Tensor, *, bias=None, residual=None, act=N
     lay = gemm4_layout(a, b)
     if lay is None:
         raise ValueError(f"matmul4: unsupported operands {tuple(a.shape)}{a.stride()} @ {tuple(b.shape)}{b.stride()}")
-    at, bt, lda, ldb = lay
-    M, K = a.shape
-    N = b.shape[1]
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    if residual is not None:
-        assert residual.shape == (M, N) and residual.stride(1) == 1 and residual.dtype == torch.bfloat16
+    M, N = a.shape[0], b.shape[1]
     if bias is not None:
         assert bias.dtype == torch.bfloat16 and bias.numel() == N and bias.is_contiguous()
         bias = _aligned_bias(bias)
-    plain = bias is None and residual is None and act is None and variant == 1
-    # the K split also carries a bias (added in the fixup, forward layout)
-    splittable = residual is None and act is None and variant == 1 and (
-        bias is None or (not at and not bt and bias.data_ptr() % 16 == 0))
-    ks = splitk_factor(M, N, K, _device_cus(a.device)) if splittable else 0
-    if ks:
-        nwg = -(-M // 256) * -(-N // 256)
-        ws = _workspace(ks * nwg * 256 * 256, a.device)
-        rc = require().lta_gemm4_bf16_splitk(a.data_ptr(), b.data_ptr(), out.data_ptr(),
-                                             None if bias is None else bias.data_ptr(), M, N, K, lda, ldb,
-                                             out.stride(0), alpha, at, bt, ks, ws.data_ptr(), ws.numel() * 4,
-                                             stream_ptr(a.device))
-        check(rc, "lta_gemm4_bf16_splitk")
-        return out
-    ws = _tail_workspace(M, N, K, a.device) if plain else None
-    if ws is not None:
-        rc = require().lta_gemm4_bf16_ws(a.data_ptr(), b.data_ptr(), out.data_ptr(), None, None, M, N, K, lda, ldb,
-                                         out.stride(0), 0, alpha, ACT[act], at, bt, variant, ws.data_ptr(),
-                                         ws.numel() * 4, stream_ptr(a.device))
-        check(rc, "lta_gemm4_bf16_ws")
-        return out
-    rc = require().lta_gemm4_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(),
-                                  None if bias is None else bias.data_ptr(),
-                                  None if residual is None else residual.data_ptr(), M, N, K, lda, ldb, out.stride(0),
-                                  0 if residual is None else residual.stride(0), alpha, ACT[act], at, bt, variant,
-                                  stream_ptr(a.device))
-    check(rc, "lta_gemm4_bf16")
-    return out
+    # decided per call (no cached record): scripts toggle the split switches between calls
+    return _run(_gemm4_launch(a, lay, bias, residual, act, variant, None, (M, N)), a, b, bias, residual, alpha, out)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -415,19 +406,144 @@ _GEMM4_VARIANTS: dict = {}
 
 
 # ---------------------------------------------------------------------------------------------
-# launch plans: the dispatch decision of a GEMM call site depends only on its operands' shapes,
-# strides, dtypes, 16-B alignment and the LTA_GEMM mode, which a compiled program repeats on every
-# call; the plan caches that decision with the kernel's scalar arguments, so a repeated call costs the
-# output allocation and one native launch (the host path of launch-bound programs, benchmarks/targets.py)
+# the dispatch rule, once: _decide turns a call's operands into a GemmLaunch record, _run launches a
+# record.  The decision depends only on the operands' shapes, strides, dtypes, 16-B alignment, the
+# activation, the device and the LTA_GEMM mode, which a compiled program repeats on every call, so
+# linear / matmul cache the record per call site: a repeated call costs the key, the output allocation
+# and one native launch (the host path of launch-bound programs, benchmarks/targets.py).  The module
+# switches _TAIL_SPLIT / _SPLITK and the _GEMM4_VARIANTS table are read when a site is decided: flipping
+# one later does not reach recorded sites, so A/B them through matmul4 (never cached) or in a new process
 # ---------------------------------------------------------------------------------------------
-_PLANS: dict = {}
-_NO_PLAN = object()
+GEMV, GEMM4, GEMM4_SPLITK, GEMM4_TAIL = "gemv", "gemm4", "gemm4_splitk", "gemm4_tail"
+GEMM_NT, GEMM_LAYOUT, TORCH_LINEAR, TORCH_MM = "gemm_nt", "gemm_layout", "torch_linear", "torch_mm"
+# entry point -> the backend last_gemm_backend_counts reports
+_BACKEND = {GEMV: "gemv", GEMM4: "gemm4", GEMM4_SPLITK: "gemm4", GEMM4_TAIL: "gemm4", GEMM_NT: "gemm",
+            GEMM_LAYOUT: "gemm", TORCH_LINEAR: "torch", TORCH_MM: "torch"}
+_GEMM4_SYMBOL = {GEMM4: "lta_gemm4_bf16", GEMM4_SPLITK: "lta_gemm4_bf16_splitk", GEMM4_TAIL: "lta_gemm4_bf16_ws"}
 
 
-def _remember(key, plan) -> None:
-    if len(_PLANS) >= 8192:  # bounded: a program seeing ever new sizes re-dispatches instead of growing
-        _PLANS.clear()
-    _PLANS[key] = plan or _NO_PLAN
+class GemmLaunch(NamedTuple):
+    """One decided GEMM call: the entry point and its scalar arguments (the gemm4 entries use all of
+    them; the other entry points read pitches from their 2-D operands)."""
+    entry: str
+    M: int
+    N: int
+    K: int
+    act: str | None = None  # key of ACT
+    lda: int = 0
+    ldb: int = 0
+    ldr: int = 0  # residual pitch (0: none)
+    at: int = 0
+    bt: int = 0
+    variant: int = 0
+    ksplit: int = 0  # GEMM4_SPLITK: K slices per tile
+    tail: int = 0  # GEMM4_TAIL: tiles of the last wave run as two K halves
+    ws: int = 0  # fp32 workspace elements of the two split entries
+    shape: tuple = ()  # the result's shape: (M, N) with the leading dims of the call site's ``a`` restored
+
+
+def _gemm4_launch(a, lay, bias, residual, act, variant, cus, shape) -> GemmLaunch:
+    """The gemm4 entry for operands of layout ``lay`` (from gemm4_layout): K split, wave-tail split or plain."""
+    at, bt, lda, ldb = lay
+    M, K = a.shape
+    N = shape[-1]
+    assert _residual_ok(residual, (M, N), rows16=False)
+    d = GemmLaunch(GEMM4, M, N, K, act, lda, ldb, 0 if residual is None else residual.stride(0), at, bt, variant,
+                   shape=shape)
+    nwg = -(-M // 256) * -(-N // 256)
+    # the K split also carries a bias (added in the fixup, forward layout)
+    if residual is None and act is None and variant == 1 and (
+            bias is None or (not at and not bt and bias.data_ptr() % 16 == 0)):
+        cus = cus or _device_cus(a.device)
+        ks = splitk_factor(M, N, K, cus)
+        if ks:
+            return d._replace(entry=GEMM4_SPLITK, ksplit=ks, ws=ks * nwg * 256 * 256)
+        tail = tail_tiles(M, N, K, cus) if bias is None else 0
+        if tail:
+            return d._replace(entry=GEMM4_TAIL, tail=tail, ws=2 * tail * 256 * 256)
+    return d
+
+
+def _decide(a, b, bias, residual, act, mode, *, linear: bool, cus: int | None = None, shape=None) -> GemmLaunch:
+    """The launch of ``act(a @ b + bias) + residual`` for a 2-D ``a [M,K]`` under the ``LTA_GEMM``
+    ``mode``, by the static rule (no run-time timing).  ``linear``: ``b`` is the weight ``[N,K]`` (the
+    product is ``a @ b.t()``): the weight-streaming GEMV for <= 8 rows, gemm4 (M >= 64, N % 8, K % 128:
+    edge tiles), the 8-wave NT kernel when tile-divisible with K % 64, else torch.  Otherwise ``b`` is
+    ``[K,N]`` in any layout (the prim matmul): gemm4, the 8-wave layout kernel, else torch.  _run takes
+    the same ``b``.  ``cus``: the device's compute units (read from the device when None); ``shape``: the
+    result's shape when the caller flattened leading dims of ``a`` (default ``(M, N)``)."""
+    M, K = a.shape
+    N = b.shape[0] if linear else b.shape[1]
+    shape = (M, N) if shape is None else tuple(shape)
+    if mode == "torch":
+        return GemmLaunch(TORCH_LINEAR if linear else TORCH_MM, M, N, K, act, shape=shape)
+    if linear:
+        if gemv_supported(a, b, bias, residual):
+            return GemmLaunch(GEMV, M, N, K, act, shape=shape)
+        lay = gemm4_layout(a, b.t())
+        if lay is not None and nt_epilogue_ok(a, b, bias, residual):
+            return _gemm4_launch(a, lay, bias, residual, act, gemm4_variant(0, 0, M, N, K), cus, shape)
+        return GemmLaunch(GEMM_NT if gemm_nt_supported(a, b, bias, residual) else TORCH_LINEAR, M, N, K, act,
+                          shape=shape)
+    if _residual_ok(residual):
+        lay = gemm4_layout(a, b)
+        if lay is not None:
+            return _gemm4_launch(a, lay, None, residual, None, gemm4_variant(lay[0], lay[1], M, N, K), cus, shape)
+        if matmul_layout(a, b) is not None:
+            return GemmLaunch(GEMM_LAYOUT, M, N, K, shape=shape)
+    return GemmLaunch(TORCH_MM, M, N, K, shape=shape)
+
+
+def _run(d: GemmLaunch, a, b, bias, residual, alpha: float = 1.0, out=None) -> torch.Tensor:
+    """Launch ``d`` on the operands _decide saw (``b`` as given there: the weight ``[N,K]`` for the
+    entries of the linear rule), or on a later call of that site.  The gemm4 entries read pointers
+    only, so ``a`` / ``residual`` may keep their leading dims."""
+    entry, M, N, K, act, lda, ldb, ldr, at, bt, variant, ksplit, _, need, shape = d
+    backend = _BACKEND[entry]
+    _backend_counts[backend] = _backend_counts.get(backend, 0) + 1
+    if entry in _GEMM4_SYMBOL:
+        dev = a.device
+        if out is None:
+            out = torch.empty(shape, dtype=torch.bfloat16, device=dev)
+            ldc = N
+        else:
+            ldc = out.stride(0)
+        pbias = None if bias is None else bias.data_ptr()
+        if entry == GEMM4:
+            rc = require().lta_gemm4_bf16(a.data_ptr(), b.data_ptr(), out.data_ptr(), pbias,
+                                          None if residual is None else residual.data_ptr(), M, N, K, lda, ldb, ldc,
+                                          ldr, alpha, ACT[act], at, bt, variant, stream_ptr(dev))
+        else:  # the workspace per call: inside a graph capture it comes from the graph's pool
+            ws = _workspace(need, dev)
+            if entry == GEMM4_SPLITK:
+                rc = require().lta_gemm4_bf16_splitk(a.data_ptr(), b.data_ptr(), out.data_ptr(), pbias, M, N, K, lda,
+                                                     ldb, ldc, alpha, at, bt, ksplit, ws.data_ptr(), ws.numel() * 4,
+                                                     stream_ptr(dev))
+            else:
+                rc = require().lta_gemm4_bf16_ws(a.data_ptr(), b.data_ptr(), out.data_ptr(), None, None, M, N, K, lda,
+                                                 ldb, ldc, 0, alpha, ACT[act], at, bt, variant, ws.data_ptr(),
+                                                 ws.numel() * 4, stream_ptr(dev))
+        if rc != 0:
+            check(rc, _GEMM4_SYMBOL[entry])
+        return out
+    if a.dim() != 2:
+        a = a.reshape(M, K)
+    if residual is not None and residual.dim() != 2:
+        residual = residual.reshape(M, N)
+    if entry == GEMV:
+        y = gemv_nt(a, b, bias=bias, residual=residual, act=act)
+    elif entry == GEMM_NT:
+        y = gemm_nt(a, b, bias=bias, residual=residual, act=act)
+    elif entry == GEMM_LAYOUT:
+        y = matmul_hip(a, b, residual=residual)
+    elif entry == TORCH_LINEAR:
+        y = _torch_linear(a, b, bias, residual, act)
+    else:
+        y = _torch_mm(a, b, residual)
+    return y.reshape(shape)
+
+
+_PLANS: dict = {}  # call site key -> GemmLaunch
 
 
 def _aligned_bias(bias):
@@ -443,108 +559,32 @@ def _tkey(t):
     return None if t is None else (t.shape, t.stride(), t.dtype, t.data_ptr() & 15)
 
 
-def _gemm4_plan(M: int, N: int, K: int, lda: int, ldb: int, at: int, bt: int, variant: int, act_code: int,
-                has_bias: bool, has_res: bool, ldr: int, out_shape, dev):
-    """A plain / bias / residual / activation gemm4 launch (no K split, no tail split) as a closure."""
-    fn = require().lta_gemm4_bf16
-    bf16 = torch.bfloat16
-
-    def run(a, b, bias, residual):
-        _backend_counts["gemm4"] = _backend_counts.get("gemm4", 0) + 1
-        out = torch.empty(out_shape, dtype=bf16, device=dev)
-        rc = fn(a.data_ptr(), b.data_ptr(), out.data_ptr(), bias.data_ptr() if has_bias else None,
-                residual.data_ptr() if has_res else None, M, N, K, lda, ldb, N, ldr, 1.0, act_code, at, bt, variant,
-                stream_ptr(dev))
-        if rc != 0:
-            check(rc, "lta_gemm4_bf16")
-        return out
-
-    return run
-
-
-def _gemm4_plain_plan(M, N, K, at, bt, lda, ldb, variant, bias, residual, act, out_shape, dev):
-    """The plan of a gemm4 product, or None when this call takes a K split / tail split (workspace per call)."""
-    plain = bias is None and residual is None and act is None and variant == 1
-    splittable = residual is None and act is None and variant == 1 and (
-        bias is None or (not at and not bt and bias.data_ptr() % 16 == 0))
-    if splittable and splitk_factor(M, N, K, _device_cus(dev)):
-        return None
-    if plain and _TAIL_SPLIT and K % 256 == 0:
-        cus = _device_cus(dev)
-        nwg = -(-M // 256) * -(-N // 256)
-        tail = nwg % cus
-        if not (nwg <= cus or tail == 0 or 2 * tail > cus):
-            return None
-    return _gemm4_plan(M, N, K, lda, ldb, at, bt, variant, ACT[act], bias is not None, residual is not None,
-                       0 if residual is None else residual.stride(0), out_shape, dev)
+def _remember(key, d: GemmLaunch, t, t2, r, r2) -> None:
+    """Record a site's decision when it can replay on the caller's own tensors (the reshapes to ``t2`` /
+    ``r2`` were views, the residual has the result's shape) and nothing is being captured into a graph."""
+    if (t.is_cuda and t2.data_ptr() == t.data_ptr()
+            and (r is None or (r2.data_ptr() == r.data_ptr() and r.shape == d.shape))
+            and not torch.cuda.is_current_stream_capturing()):
+        if len(_PLANS) >= 8192:  # bounded: a program seeing ever new sizes decides again instead of growing
+            _PLANS.clear()
+        _PLANS[key] = d
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act=None) -> torch.Tensor:
-    """``act(x @ w.T + bias) + residual`` on the hand-written kernels, chosen by a static rule:
-    the weight-streaming GEMV for <= 8 rows, the 4-wave MFMA GEMM (csrc/gemm4.hip, any M >= 64,
-    N % 8, K % 128: edge tiles), the 8-wave kernel (csrc/gemm.hip) when tile-divisible with K % 64,
-    else torch (``LTA_GEMM=torch`` forces torch).  Repeated call sites run a cached launch plan."""
+    """``act(x @ w.T + bias) + residual`` on the kernel :func:`_decide` picks (``LTA_GEMM=torch`` forces
+    torch).  A repeated call site runs its cached decision."""
     bias = _aligned_bias(bias)
-    key = ("lin", _tkey(x), _tkey(w), _tkey(bias), _tkey(residual), act, x.get_device(),
-           _os.environ.get("LTA_GEMM", "auto"))
-    plan = _PLANS.get(key)
-    if plan is not None and plan is not _NO_PLAN and x.is_cuda:
-        return plan(x, w, bias, residual)
-    out = _linear_dispatch(x, w, bias, residual, act)
-    if plan is None and x.is_cuda and not torch.cuda.is_current_stream_capturing():
-        _remember(key, _linear_plan(x, w, bias, residual, act))
-    return out
-
-
-def _linear_plan(x, w, bias, residual, act):
-    """The cached form of :func:`_linear_dispatch` for this call's operands (gemm4 launches only)."""
-    if _os.environ.get("LTA_GEMM", "auto") == "torch":
-        return None
-    K = x.shape[-1]
-    N = w.shape[0]
-    x2 = x.reshape(-1, K)
-    r2 = None if residual is None else residual.reshape(-1, N)
-    if gemv_supported(x2, w, bias, r2):
-        return None
-    if _FWD_LIB and act is None and bias is None and x2.shape[0] >= 1024 and x2.dtype == torch.bfloat16:
-        return None
-    wt = w.t()
-    lay = gemm4_layout(x2, wt)
-    if lay is None or not nt_epilogue_ok(x2, w, bias, r2):
-        return None
-    at, bt, lda, ldb = lay
-    M = x2.shape[0]
-    if x2.data_ptr() != x.data_ptr() or (r2 is not None and r2.data_ptr() != residual.data_ptr()):
-        return None  # a reshape that copied: the plan launches on the caller's tensors
-    return _gemm4_plain_plan(M, N, K, at, bt, lda, ldb, gemm4_variant(0, 0, M, N, K), bias, r2, act,
-                             tuple(x.shape[:-1]) + (N,), x.device)
-
-
-def _linear_dispatch(x: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act=None) -> torch.Tensor:
-    K = x.shape[-1]
-    N = w.shape[0]
-    x2 = x.reshape(-1, K)
-    r2 = None if residual is None else residual.reshape(-1, N)
     mode = _os.environ.get("LTA_GEMM", "auto")
-    if mode != "torch":
-        if gemv_supported(x2, w, bias, r2):
-            _count("gemv")
-            return gemv_nt(x2, w, bias=bias, residual=r2, act=act).reshape(*x.shape[:-1], N)
-        if _FWD_LIB and act is None and bias is None and x2.shape[0] >= 1024 and x2.dtype == torch.bfloat16:
-            # A/B hook: forward products with no epilogue but the residual on the library GEMM
-            _count("torch")
-            return _torch_linear(x2, w, bias, r2, act).reshape(*x.shape[:-1], N)
-        wt = w.t()
-        lay = gemm4_layout(x2, wt)
-        if lay is not None and nt_epilogue_ok(x2, w, bias, r2):
-            _count("gemm4")
-            y = matmul4(x2, wt, bias=bias, residual=r2, act=act, variant=gemm4_variant(0, 0, x2.shape[0], N, K))
-            return y.reshape(*x.shape[:-1], N)
-        if gemm_nt_supported(x2, w, bias, r2):
-            _count("gemm")
-            return gemm_nt(x2, w, bias=bias, residual=r2, act=act).reshape(*x.shape[:-1], N)
-    _count("torch")
-    return _torch_linear(x2, w, bias, r2, act).reshape(*x.shape[:-1], N)
+    key = ("lin", _tkey(x), _tkey(w), _tkey(bias), _tkey(residual), act, x.get_device(), mode)
+    d = _PLANS.get(key)
+    if d is None:
+        N = w.shape[0]
+        x2 = x.reshape(-1, x.shape[-1])
+        r2 = None if residual is None else residual.reshape(-1, N)
+        d = _decide(x2, w, bias, r2, act, mode, linear=True, shape=x.shape[:-1] + (N,))
+        _remember(key, d, x, x2, residual, r2)
+        x, residual = x2, r2
+    return _run(d, x, w, bias, residual)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -572,7 +612,7 @@ def matmul_layout(a: torch.Tensor, b: torch.Tensor):
         return None
     M, K = a.shape
     N = b.shape[1]
-    if b.shape[0] != K or M % TILE_M or N % TILE_N or K % TILE_K:
+    if b.shape[0] != K or not _gemm8_shape(M, N, K):
         return None
     la, lb = _operand_layout(a, M, K), _operand_layout(b, K, N)
     if la is None or lb is None:
@@ -594,8 +634,7 @@ def matmul_hip(a: torch.Tensor, b: torch.Tensor, *, residual: torch.Tensor | Non
     N = b.shape[1]
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    if residual is not None:
-        assert residual.shape == (M, N) and residual.stride(1) == 1 and residual.dtype == torch.bfloat16
+    assert _residual_ok(residual, (M, N), rows16=False)
     rc = require().lta_gemm_bf16_layout(a.data_ptr(), b.data_ptr(), out.data_ptr(),
                                         None if residual is None else residual.data_ptr(), M, N, K, lda, ldb,
                                         out.stride(0), 0 if residual is None else residual.stride(0), 1.0, at, bt,
@@ -610,67 +649,29 @@ def _torch_mm(a, b, residual=None):
 
 def matmul(a: torch.Tensor, b: torch.Tensor, residual: torch.Tensor | None = None) -> torch.Tensor:
     """``a @ b (+ residual)`` for the prim matmul (leading dims of ``a`` flattened) — the backward's
-    dgrad / wgrad read their transposed operands in place.  Static rule as :func:`linear`: the
-    4-wave kernel, else the 8-wave kernel, else torch.  Repeated call sites run a cached launch plan."""
-    key = ("mm", _tkey(a), _tkey(b), _tkey(residual), a.get_device(), _os.environ.get("LTA_GEMM", "auto"))
-    plan = _PLANS.get(key)
-    if plan is not None and plan is not _NO_PLAN and a.is_cuda:
-        return plan(a, b, None, residual)
-    out = _matmul_dispatch(a, b, residual)
-    if plan is None and a.is_cuda and not torch.cuda.is_current_stream_capturing():
-        _remember(key, _matmul_plan(a, b, residual))
-    return out
-
-
-def _matmul_plan(a, b, residual):
-    if _os.environ.get("LTA_GEMM", "auto") == "torch" or b.dim() != 2 or a.dim() < 2:
-        return None
-    a2 = a.reshape(-1, a.shape[-1]) if a.dim() > 2 else a
-    if a2.data_ptr() != a.data_ptr():
-        return None
-    N = b.shape[1]
-    r2 = None if residual is None else residual.reshape(-1, N)
-    if r2 is not None and r2.data_ptr() != residual.data_ptr():
-        return None
-    if r2 is not None and not (r2.dtype == torch.bfloat16 and r2.stride(1) == 1 and r2.stride(0) % 8 == 0
-                               and r2.data_ptr() % 16 == 0):
-        return None
-    lay = gemm4_layout(a2, b)
-    if lay is None:
-        return None
-    at, bt, lda, ldb = lay
-    M, K = a2.shape
-    return _gemm4_plain_plan(M, N, K, at, bt, lda, ldb, gemm4_variant(at, bt, M, N, K), None, r2, None,
-                             tuple(a.shape[:-1]) + (N,), a.device)
-
-
-def _matmul_dispatch(a: torch.Tensor, b: torch.Tensor, residual: torch.Tensor | None = None) -> torch.Tensor:
-    if a.dim() > 2 and b.dim() == 2:
-        lead = a.shape[:-1]
-        a2 = a.reshape(-1, a.shape[-1])
-        r2 = None if residual is None else residual.reshape(-1, b.shape[1])
-        return _matmul_dispatch(a2, b, r2).reshape(*lead, b.shape[1])
+    dgrad / wgrad read their transposed operands in place — on the kernel :func:`_decide` picks.  A
+    repeated call site runs its cached decision."""
+    if b.dim() != 2 or a.dim() < 2:  # no 2-D product: the library's broadcasting matmul
+        _count("torch")
+        return _torch_mm(a, b, residual)
     mode = _os.environ.get("LTA_GEMM", "auto")
-    res_ok = residual is None or (residual.dtype == torch.bfloat16 and residual.stride(1) == 1
-                                  and residual.stride(0) % 8 == 0 and residual.data_ptr() % 16 == 0)
-    if mode != "torch" and res_ok:
-        lay = gemm4_layout(a, b)
-        if lay is not None:
-            _count("gemm4")
-            return matmul4(a, b, residual=residual,
-                           variant=gemm4_variant(lay[0], lay[1], a.shape[0], b.shape[1], a.shape[1]))
-        if matmul_layout(a, b) is not None:
-            _count("gemm")
-            return matmul_hip(a, b, residual=residual)
-    _count("torch")
-    return _torch_mm(a, b, residual)
+    key = ("mm", _tkey(a), _tkey(b), _tkey(residual), a.get_device(), mode)
+    d = _PLANS.get(key)
+    if d is None:
+        N = b.shape[1]
+        a2, r2 = a, residual
+        if a.dim() > 2:
+            a2 = a.reshape(-1, a.shape[-1])
+            r2 = None if residual is None else residual.reshape(-1, N)
+        d = _decide(a2, b, None, r2, None, mode, linear=False, shape=a.shape[:-1] + (N,))
+        _remember(key, d, a, a2, residual, r2)
+        a, residual = a2, r2
+    return _run(d, a, b, None, residual)
 
 
 # ---------------------------------------------------------------------------------------------
 # K10 grouped GEMM (mixture of experts)
 # ---------------------------------------------------------------------------------------------
-from ._lib import c_int64  # noqa: E402
-
 register_signature("lta_gemm_grouped_nt_bf16", [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                                 c_int64, c_void_p])
 
@@ -706,12 +707,10 @@ def _grouped_b_layout(b: torch.Tensor):
 def grouped_rows_supported(a: torch.Tensor, b: torch.Tensor, offs: torch.Tensor) -> bool:
     """The 2-D x 3-D grouped form on the 4-wave kernel (mode 1): a [M, K] row-major, b [G, K, N] in
     either per-group layout, K % 128, N % 8."""
-    if not (a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.dim() == 2 and b.dim() == 3):
+    if not (_plain_2d(a) and b.dtype == torch.bfloat16 and b.dim() == 3):
         return False
     G, K, N = b.shape
     if a.shape[1] != K or K % 128 or N % 8 or offs is None or offs.dtype != torch.int32 or offs.numel() != G:
-        return False
-    if not (a.stride(1) == 1 and a.stride(0) % 8 == 0 and a.data_ptr() % 16 == 0):
         return False
     return _grouped_b_layout(b) is not None and b.stride(0) * G * 2 < 2 ** 62
 
@@ -795,11 +794,6 @@ def _fused_swiglu_on() -> bool:
     or the per-tile a / b loads (down-projection dgrad + swiglu backward: 382 us per layer) cost about
     what the separate streaming passes they remove cost."""
     return _os.environ.get("LTA_FUSED_SWIGLU", "0") == "1"
-
-
-def _plain_2d(t: torch.Tensor) -> bool:
-    return (t.dim() == 2 and t.dtype == torch.bfloat16 and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 8 == 0
-            and t.data_ptr() % 16 == 0)
 
 
 def gate_up_supported(x2: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor) -> bool:

@@ -1454,9 +1454,8 @@ def test_layer_norm_backward_residual_fused(cols):
 def test_gemm4_wave_tail_split(M, N, K, layout):
     """Plain products whose tile grid ends in a partial wave (<= 128 tiles) run that tail as two K
     halves + an fp32 fixup (csrc/gemm4.hip launch4_tail): vs an fp32 reference in every layout."""
-    from lightning_thunder_amd.ops.gemm import matmul4, _tail_workspace
+    from lightning_thunder_amd.ops.gemm import matmul4, _decide, GEMM4_TAIL
 
-    assert _tail_workspace(M, N, K, "cuda") is not None  # the shape takes the split path
     torch.manual_seed(0)
     if layout[0] == "n":
         a = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
@@ -1466,6 +1465,8 @@ def test_gemm4_wave_tail_split(M, N, K, layout):
         b = torch.randn(N, K, device="cuda", dtype=torch.bfloat16).t()
     else:
         b = torch.randn(K, N, device="cuda", dtype=torch.bfloat16)
+    # the shape takes the split path
+    assert _decide(a, b, None, None, None, "auto", linear=False).entry == GEMM4_TAIL
     out = matmul4(a, b)
     ref = a.float() @ b.float()
     err = ((out.float() - ref).norm() / ref.norm()).item()
@@ -1639,28 +1640,58 @@ def test_fp8_gemm_qkv_rope_matches_unfused(B, T, nh, ng, K):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("bias,act", [(False, None), (True, None), (True, "gelu_tanh")])
-def test_gemm4_linear_plan_repeats(bias, act):
-    """Repeated linear calls at one site run the cached launch plan: the first call dispatches and
-    records it, the replays give the same result, and every call matches fp32."""
+def test_gemm4_linear_plan_repeats(bias, act, monkeypatch):
+    """Repeated calls at one site run the cached decision: the first call decides and records it, the
+    replays give the same result, and every call matches fp32.  The sites: plain gemm4 products, and
+    the decisions that take a workspace or another kernel per call (split-K, tail split, GEMV, a
+    split-K wgrad through matmul), each checked to take that path on this device."""
     from lightning_thunder_amd.ops import gemm as G
 
+    decide, decided = G._decide, []
+    monkeypatch.setattr(G, "_decide", lambda *a, **kw: decided.append(decide(*a, **kw)) or decided[-1])
+    monkeypatch.setattr(G, "_PLANS", {})  # every site below is new
+    plain = not bias and act is None
+    splitk = G.GEMM4_SPLITK if act is None else G.GEMM4  # 48 and 16 tiles: under half a wave
+    sites = [((8, 256, 1536), 4608, G.GEMM4), ((8, 256, 6144), 1536, splitk), ((8, 125, 256), 16032, G.GEMM4),
+             ((8, 128, 1024), 1024, splitk),
+             ((512, 256), 33024, G.GEMM4_TAIL if plain else G.GEMM4),
+             ((4, 512), 512, G.GEMV)]
     torch.manual_seed(0)
-    for M, N, K in ((2048, 4608, 1536), (2048, 1536, 6144), (1000, 16032, 256)):
-        x = torch.randn(8, M // 8, K, device="cuda", dtype=torch.bfloat16)
+    for xs, N, entry in sites:
+        K = xs[-1]
+        x = torch.randn(*xs, device="cuda", dtype=torch.bfloat16)
         w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) / K ** 0.5
         bb = torch.randn(N, device="cuda", dtype=torch.bfloat16) if bias else None
+        assert decide(x.reshape(-1, K), w, bb, None, act, "auto", linear=True).entry == entry, (xs, N)
         G.last_gemm_backend_counts(reset=True)
+        del decided[:]
         outs = [G.linear(x, w, bb, act=act) for _ in range(3)]
         counts = G.last_gemm_backend_counts(reset=True)
-        assert counts.get("gemm4", 0) == 3 and counts.get("torch", 0) == 0, counts
+        assert counts == {G._BACKEND[entry]: 3}, counts
+        assert [d.entry for d in decided] == [entry], decided  # decided once, replayed twice
         ref = x.float() @ w.float().t() + (bb.float() if bias else 0)
         if act == "gelu_tanh":
             ref = torch.nn.functional.gelu(ref, approximate="tanh")
         for o in outs:
-            assert o.shape == (8, M // 8, N)
+            assert o.shape == xs[:-1] + (N,)
             torch.testing.assert_close(o, outs[0], rtol=0, atol=0)
         err = ((outs[0].float() - ref).norm() / ref.norm()).item()
-        assert err < 1e-2, (M, N, K, err)
+        assert err < 1e-2, (xs, N, err)
+    if plain:  # wgrad layout: g^T @ x read in place, an under-filled grid
+        g = torch.randn(2048, 1024, device="cuda", dtype=torch.bfloat16)
+        x = torch.randn(2048, 1536, device="cuda", dtype=torch.bfloat16)
+        d = decide(g.t(), x, None, None, None, "auto", linear=False)
+        assert (d.entry, d.at, d.bt) == (G.GEMM4_SPLITK, 1, 1), d
+        del decided[:]
+        outs = [G.matmul(g.t(), x) for _ in range(3)]
+        assert G.last_gemm_backend_counts(reset=True) == {"gemm4": 3}
+        assert decided == [d], decided
+        ref = g.float().t() @ x.float()
+        for o in outs:
+            assert o.shape == (1024, 1536)
+            torch.testing.assert_close(o, outs[0], rtol=0, atol=0)
+        err = ((outs[0].float() - ref).norm() / ref.norm()).item()
+        assert err < 1e-2, err
 
 
 @pytest.mark.gpu
