@@ -4,7 +4,8 @@ Thunder + CUDAGraphs 542 ms on 1x H100).
 
 Same task on MI355X with the LitGPT-architecture Llama-3.2-1B (random-init weights, synthetic
 prompt; no checkpoints offline): greedy decoding of ``--new-tokens`` tokens after a
-``--prompt-len`` token prompt with a static KV cache, bf16.  Modes:
+``--prompt-len`` token prompt with a static KV cache, bf16 (``--temperature`` > 0 with ``--top-k`` /
+``--top-p`` / ``--seed``: sampled decoding through ``ops.sampling.sample_last``, LitGPT modes only).  Modes:
 
 * ``eager``    — PyTorch eager (ROCm), same model code;
 * ``thunder``  — ``jit(model)``: prefill and decode are two cached programs (hipex/hipfuse kernels,
@@ -68,6 +69,7 @@ def run(mode: str, args) -> dict:
     from ..models.litgpt import generate
 
     device = torch.device("cuda", 0)
+    sampling = args.temperature > 0 and not mode.startswith("hf_")  # the HF modes stay greedy
     if mode.startswith("hf_"):
         # the reference's benchmark: HF transformers model.generate with a static cache
         model, cfg = _build_hf(device, args.n_layer)
@@ -102,7 +104,10 @@ def run(mode: str, args) -> dict:
             fwd = thunder.jit(model, transforms=transforms)
 
         def once():
-            return generate(model, prompt, args.new_tokens, forward=fwd)
+            if sampling:  # every timed generation draws the same tokens
+                torch.manual_seed(args.seed)
+            return generate(model, prompt, args.new_tokens, forward=fwd, temperature=args.temperature,
+                            top_k=args.top_k, top_p=args.top_p)
 
     t0 = time.perf_counter()
     out = once()
@@ -120,7 +125,7 @@ def run(mode: str, args) -> dict:
         times.append(time.perf_counter() - t0)
     ms = 1000 * sum(times) / len(times)
     res = {
-        "metric": f"{args.model} greedy generate latency ({args.new_tokens} new tokens, static KV cache)",
+        "metric": f"{args.model} {'sampled' if sampling else 'greedy'} generate latency ({args.new_tokens} new tokens, static KV cache)",
         "model_impl": "transformers.LlamaForCausalLM" if mode.startswith("hf_") else "lightning_thunder_amd litgpt GPT",
         "mode": mode, "value": round(ms, 2), "unit": "ms", "higher_is_better": False,
         "ms_per_token": round(ms / args.new_tokens, 3), "first_call_s": round(first, 2),
@@ -129,6 +134,8 @@ def run(mode: str, args) -> dict:
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
         "reference_ms": {"thunder+cudagraphs (1xH100)": 542, "eager (1xH100)": 1493},
     }
+    if sampling:
+        res.update(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     res["tokens"] = out[0, -args.new_tokens:].tolist()
     return res
 
@@ -151,6 +158,10 @@ def main(argv=None):
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--modes", default="eager,thunder,hipgraph")
     p.add_argument("--n-layer", type=int, default=None, help="debug only")
+    p.add_argument("--temperature", type=float, default=0.0, help="> 0: sample (LitGPT modes only) instead of greedy")
+    p.add_argument("--top-k", type=int, default=None)
+    p.add_argument("--top-p", type=float, default=None)
+    p.add_argument("--seed", type=int, default=0, help="torch.manual_seed before every sampled generation")
     args = p.parse_args(argv)
     results = []
     ref = {}  # model family -> tokens of its eager mode
@@ -159,7 +170,7 @@ def main(argv=None):
         fam = "hf" if mode.startswith("hf_") else "litgpt"
         if mode in ("eager", "hf_eager"):
             ref[fam] = r["tokens"]
-        if fam in ref:
+        if fam in ref and "temperature" not in r:  # sampled runs draw from different streams: no such check
             # greedy decoding of a random-init model: logits are nearly flat, so one bf16 rounding
             # difference flips an argmax and the continuation diverges; the leading tokens that agree
             # with eager are the numerics check

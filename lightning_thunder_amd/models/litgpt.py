@@ -477,16 +477,20 @@ def flops_per_token(config: Config, seq_len: int, training: bool = True) -> floa
 
 @torch.no_grad()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, temperature: float = 0.0,
-             top_k: Optional[int] = None, eos_id: Optional[int] = None) -> torch.Tensor:
+             top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id: Optional[int] = None) -> torch.Tensor:
     """Autoregressive generation with the static KV cache (LitGPT ``generate``).
 
     ``forward`` is the callable used for every step (default: ``model``; pass ``thunder.jit(model)``).
     Prefill runs the prompt with ``input_pos = arange(T)``; every decode step feeds one token with
     the *same* ``input_pos`` tensor advanced in place, so a compiled decode step keeps its input
     addresses (hipGraph-replayable) and is a cache hit after the first token.
-    Greedy when ``temperature == 0``.  Returns ``[B, T + max_new_tokens]`` token ids.
+    Greedy when ``temperature == 0``.  With ``temperature > 0`` every token is drawn by
+    ``ops.sampling.sample_last``: temperature, then ``top_k`` (ties at the k-th logit all stay drawable),
+    then the nucleus ``top_p``, then one draw from the softmax of what is left.  The draws come from the
+    project's Philox counter stream (``core.rng``), not from ATen's generator: ``torch.manual_seed(s)``
+    before the call reproduces the tokens.  Returns ``[B, T + max_new_tokens]`` token ids.
     """
-    from ..ops.sampling import argmax_last
+    from ..ops.sampling import argmax_last, sample_last
 
     forward = forward or model
     B, T = prompt.shape
@@ -500,11 +504,7 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
     for i in range(max_new_tokens):
         last = logits[:, -1]
         if temperature > 0:
-            last = last / temperature
-            if top_k is not None:
-                v, _ = torch.topk(last, min(top_k, last.size(-1)))
-                last = torch.where(last < v[:, [-1]], torch.full_like(last, -float("inf")), last)
-            nxt = torch.multinomial(torch.softmax(last.float(), -1), 1)
+            nxt = sample_last(last, temperature, top_k, top_p, keepdim=True)
         else:
             nxt = argmax_last(last, keepdim=True)
         out.append(nxt)
