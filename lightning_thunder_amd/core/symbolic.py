@@ -436,6 +436,69 @@ def static_value(x):
     return int.__int__(x) if isinstance(x, SymInt) else x
 
 
+def _pinned(env: ShapeEnv, atom: str):
+    """The constant a recorded ``== c`` guard pins symbol ``atom`` (or a symbol recorded equal to it) to."""
+    if atom not in env._parent:
+        return None
+    traced = {n: v for n, _, _, v in env.symbols}
+    for n in env.equivalents(atom):
+        v = traced.get(n)
+        if v is not None and (env.guards.get(f"{n} == {v}") is True or env.guards.get(f"({n}) == {v}") is True):
+            return v
+    return None
+
+
+def _canonical_poly(x, env: ShapeEnv | None) -> dict:
+    """``x`` as a polynomial over one representative per class of symbols recorded equal, with pinned
+    symbols folded into the coefficients."""
+    if not isinstance(x, SymInt):
+        return {(): int(x)} if x else {}
+    if env is None:
+        return x.poly
+    out: dict = {}
+    for m, c in x.poly.items():
+        atoms = []
+        for a in m:
+            k = _pinned(env, a)
+            if k is not None:
+                c *= k
+            else:
+                atoms.append(env._find(a))
+        key = tuple(sorted(atoms))
+        v = out.get(key, 0) + c
+        if v:
+            out[key] = v
+        else:
+            out.pop(key, None)
+    return out
+
+
+def known_constant(x):
+    """The value of a dim that is the same for every size the program admits: a plain int, or a SymInt the
+    shape environment has already pinned with a recorded ``== c`` guard; else None.  Records nothing."""
+    if not isinstance(x, SymInt):
+        return int(x)
+    env = _env.get()
+    if env is None:
+        return None
+    v = int.__int__(x)
+    if env.guards.get(f"{x.expr} == {v}") is True or env.guards.get(f"({x.expr}) == {v}") is True:
+        return v
+    p = _canonical_poly(x, env)
+    if not p:
+        return 0
+    return p[()] if list(p) == [()] else None
+
+
+def same_dim(a, b) -> bool:
+    """Are two dims equal at every size the guards recorded so far admit (the same expression up to
+    recorded equalities and pinned symbols)?  Records nothing: a False only says it is not proven."""
+    if not isinstance(a, SymInt) and not isinstance(b, SymInt):
+        return a == b
+    env = _env.get()
+    return _canonical_poly(a, env) == _canonical_poly(b, env)
+
+
 class SymShape(tuple):
     """A tensor proxy's shape when some dims are symbolic (``torch.Size`` would turn them into plain
     ints through ``__index__``).  Behaves like ``torch.Size`` for the calls traced code makes."""

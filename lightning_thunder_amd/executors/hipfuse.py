@@ -14,6 +14,8 @@ Each region becomes one ``hipFusionN`` callable: Python generates HIP source per
 signature (input strides + alignment), the native runtime (``ops/csrc/runtime/rtc.cpp``)
 compiles it with hiprtc for gfx950 and launches it on the current HIP stream.  Code
 objects are cached in memory and on disk (``$LTA_CACHE_DIR`` or ``ops/_build/rtc_cache``).
+A region with symbolic dims (``cache="symbolic values"``) is one runtime-sized kernel per
+stride / alignment class: each call binds the extents from its tensors (``HipFusion._call``).
 """
 from __future__ import annotations
 
@@ -28,7 +30,7 @@ from ..core.rng import GraphRngInt
 
 import torch
 
-from ..core.symbolic import SymInt
+from ..core.symbolic import SymInt, known_constant, static_value
 
 from ..core import profile as _profile
 from ..core.prims import PrimIDs, OpTags
@@ -57,37 +59,52 @@ ex.allow_cpu = False  # tests flip this to exercise partitioning/codegen on CPU 
 _counter = itertools.count()
 
 
-def _checker(*args, **kwargs):
-    dev = kwargs.get("device")
-    if dev is not None and getattr(dev, "type", None) not in (None, "cuda") and not ex.allow_cpu:
+def _symbolic_ok(sid, args) -> bool:
+    """Symbolic dims (cache="symbolic values"): the prims whose kernels take their sizes at run time
+    (``hipfuse_codegen.SYMBOLIC_OK``).  Reshapes may only add or drop unit dims and reductions run over
+    trailing dims of constant extent; everything else stays on the per-op executors, so one program
+    serves every size.  Nothing here records a guard."""
+    if sid not in cg.SYMBOLIC_OK:
         return False
-    for a in tree_flatten((args, kwargs))[0]:
-        if isinstance(a, TensorProxy):
-            if not cg.supported_dtype(a.dtype):
-                return False
-            if a.device.type != "cuda" and not ex.allow_cpu:
-                return False
-            if any(not isinstance(s, int) or isinstance(s, SymInt) for s in a.shape):
-                # symbolic dims (cache="symbolic values"): generated kernels bake their sizes in, so
-                # these ops stay on the per-op executors and one program serves every size
-                return False
+    if sid == PrimIDs.RESHAPE:
+        return cg._seq(cg._sq(args[0].shape), cg._sq(tuple(args[1])))
+    if sid in cg.REDUCTIONS:
+        a, dims = args[0], tuple(sorted(args[1]))
+        return dims == tuple(range(a.ndim - len(dims), a.ndim)) and all(known_constant(a.shape[d]) is not None for d in dims)
     return True
 
 
+def _make_checker(sid):
+    def _checker(*args, **kwargs):
+        dev = kwargs.get("device")
+        if dev is not None and getattr(dev, "type", None) not in (None, "cuda") and not ex.allow_cpu:
+            return False
+        symbolic = False
+        for a in tree_flatten((args, kwargs))[0]:
+            if isinstance(a, TensorProxy):
+                if not cg.supported_dtype(a.dtype):
+                    return False
+                if a.device.type != "cuda" and not ex.allow_cpu:
+                    return False
+                if any(not isinstance(s, int) for s in a.shape):
+                    return False
+                symbolic = symbolic or any(isinstance(s, SymInt) for s in a.shape)
+            elif isinstance(a, SymInt):
+                symbolic = True  # a symbolic shape argument (full, uniform_philox, broadcast_in_dim)
+        return not symbolic or _symbolic_ok(sid, args)
+
+    return _checker
+
+
 for _sid in cg.SUPPORTED:
-    ex.register_supported(_sid, _checker)
-
-
-def _symbolic(b: BoundSymbol) -> bool:
-    return any(isinstance(p, TensorProxy) and any(isinstance(d, SymInt) for d in p._shape)
-               for p in (*b.flat_proxy_args, *b.flat_proxy_outs))
+    ex.register_supported(_sid, _make_checker(_sid))
 
 
 def _is_barrier(b: BoundSymbol) -> bool:
+    # symbolic dims are no barrier: the prims of hipfuse_codegen.SYMBOLIC_OK form runtime-sized regions,
+    # the others are refused by their checkers and run per op inside the segment
     if b.sym.id in (PrimIDs.RETURN, PrimIDs.DEL, PrimIDs.COMMENT):
         return True
-    if _symbolic(b):
-        return True  # symbolic dims: no region (kernels bake sizes in), not even a view inside one
     tags = set(b.sym.tags or ()) | set(getattr(b, "tags", ()) or ())
     if OpTags.DONT_DCE in tags or OpTags.IN_PLACE in tags or OpTags.RANDOM_OP in tags:
         return True
@@ -131,21 +148,59 @@ class HipFusion:
         self._lock = threading.Lock()
         # + the workspace pointer (column mode) in the second type
         self._argbuf_t, self._argbuf_ws_t = arg_buffer_types(len(self.tensor_pos), len(outputs), len(self.number_pos))
-        # regions have static shapes (symbolic bound symbols are fusion barriers): the output
-        # allocations are fixed once here instead of re-deriving proxy shapes on every call
-        self._out_specs = [(tuple(int(d) for d in o.shape), o.dtype) for o in outputs]
+        self.symbolic = plan.symbolic
+        if self.symbolic:
+            # a runtime-sized region (Plan.bind): every call binds its extents from its tensors, derives the
+            # output shapes and the grid from them and passes extents and strides after the usual words
+            sym = plan.sym
+            self._sym_outs = [(shape, o.dtype) for shape, o in zip(sym["out_shapes"], outputs)]
+            nwords = len(self._argbuf_t()) + len(sym["ext_bind"]) + sym["nstr"]
+            self._argbuf_t = ctypes.c_uint64 * nwords
+            self._ref_symbols = self._bind_symbols()
+            self._sym_memo: dict = {}
+            return
+        # a static region: the output allocations are fixed once here instead of re-deriving proxy shapes
+        # on every call (dims a guard pins to a constant read as that constant)
+        self._out_specs = [(tuple(static_value(d) for d in o.shape), o.dtype) for o in outputs]
         self._out_empty = any(0 in shape for shape, _ in self._out_specs)
 
     def __repr__(self):
         return f"HipFusion({self.name}, {len(self.nodes)} prims)"
 
     # -- reference path (CPU tensors; used by CPU tests of partitioning) ----------------------
+    def _bind_symbols(self) -> dict:
+        """Reference path of a symbolic region: where each symbol its prims' shape arguments print is
+        read at call time, {symbol: (tensor input, dim) or a pinned constant}."""
+        from ..core.symbolic import current_env, same_dim
+
+        env = current_env()
+        traced = {n: v for n, _, _, v in env.symbols} if env is not None else {}
+        names = set()
+        for b in self.nodes:
+            for x in tree_flatten((b.args, b.kwargs))[0]:
+                if isinstance(x, SymInt):
+                    names |= x.free_symbols()
+        tins = [self.inputs[i] for i in self.tensor_pos]
+        out = {}
+        for n in sorted(names):
+            s = SymInt(traced.get(n, 0), n)
+            c = known_constant(s)
+            out[n] = c if c is not None else next(
+                ((i, j) for i, t in enumerate(tins) for j, x in enumerate(t.shape) if same_dim(x, s)), None)
+        return out
+
     def _run_reference(self, args):
         from .torchex import ex as tex
 
         env = {p.name: a for p, a in zip(self.inputs, args) if isinstance(p, Proxy)}
+        symvals = None
+        if self.symbolic:
+            symvals = {n: (args[self.tensor_pos[w[0]]].shape[w[1]] if isinstance(w, tuple) else w)
+                    for n, w in self._ref_symbols.items()}
 
         def get(x):
+            if symvals is not None and isinstance(x, SymInt):  # a symbolic shape argument: its value at this call
+                return eval(x.expr, {"__builtins__": {}}, symvals)
             return env.get(x.name, x) if isinstance(x, Proxy) else x
 
         for b in self.nodes:
@@ -158,8 +213,9 @@ class HipFusion:
         return tuple(env[o.name] for o in self.outputs)
 
     # -- native path ---------------------------------------------------------------------------
-    def _variant(self, tensors, rng_key=()):
-        key = tuple((tuple(t.stride()), t.data_ptr() % 16 == 0) for t in tensors)
+    def _variant(self, tensors, rng_key=(), sym_key=None):
+        # a symbolic region is keyed on the classes its source bakes in (cg.sym_call), not on the strides
+        key = sym_key if sym_key is not None else tuple((tuple(t.stride()), t.data_ptr() % 16 == 0) for t in tensors)
         if rng_key:
             key = (key, rng_key)
         v = self._variants.get(key)
@@ -190,9 +246,24 @@ class HipFusion:
         dev = tensors[0].device if tensors else None
         if dev is None or dev.type != "cuda":
             return self._run_reference(args)
-        outs = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in self._out_specs]
-        if self._out_empty or any(t.numel() == 0 for t in tensors):
-            return tuple(outs)
+        sym_key = tail = grid = None
+        if self.symbolic:
+            meta = tuple((t.shape, t.stride(), t.data_ptr() % 16 == 0) for t in tensors)
+            hit = self._sym_memo.get(meta)
+            if hit is None:  # the last few call signatures are remembered (a training loop repeats its sizes)
+                sym_key, ext, words, D = cg.sym_call(self.plan, meta)
+                shapes = [[s if s >= 0 else ext[-1 - s] for s in shape] for shape, _ in self._sym_outs]
+                if len(self._sym_memo) >= 64:
+                    self._sym_memo.clear()
+                hit = self._sym_memo[meta] = (sym_key, ext + words, D, shapes, 0 in D or any(0 in m[0] for m in meta))
+            sym_key, tail, D, shapes, empty = hit
+            outs = [torch.empty(shape, dtype=dt, device=dev) for shape, (_, dt) in zip(shapes, self._sym_outs)]
+            if empty:
+                return tuple(outs)  # an empty domain: nothing to launch
+        else:
+            outs = [torch.empty(shape, dtype=dt, device=dev) for shape, dt in self._out_specs]
+            if self._out_empty or any(t.numel() == 0 for t in tensors):
+                return tuple(outs)
         numbers = [args[i] for i in self.number_pos]
         rng_key, states = (), None
         if numbers and any(type(x) is GraphRngInt for x in numbers):
@@ -207,11 +278,13 @@ class HipFusion:
                         states.append(x.state)
                     rk.append((j, x.kind, si))
             rng_key = tuple(rk)
-        (fns, ks) = self._variant(tensors, rng_key)
+        (fns, ks) = self._variant(tensors, rng_key, sym_key)
+        if tail is not None:
+            grid = (cg.sym_grid(ks.sym_mode, D, self.plan.red), 1, 1)
         if states:
-            launch(ks, fns, tensors, outs, numbers, name=self.name, rng_states=states)
+            launch(ks, fns, tensors, outs, numbers, name=self.name, rng_states=states, tail=tail, grid=grid)
         else:
-            launch(ks, fns, tensors, outs, numbers, self._argbuf_t, self._argbuf_ws_t, self.name)
+            launch(ks, fns, tensors, outs, numbers, self._argbuf_t, self._argbuf_ws_t, self.name, tail=tail, grid=grid)
         return tuple(outs)
 
 
@@ -221,13 +294,22 @@ def arg_buffer_types(n_tensors: int, n_outputs: int, n_numbers: int):
 
 
 def launch(ks: cg.KernelSource, fns: list, tensors: list, outs: list, numbers: list, argbuf_t=None, argbuf_ws_t=None,
-           name: str = "hipFusion", rng_states=None) -> None:
+           name: str = "hipFusion", rng_states=None, tail=None, grid=None) -> None:
     """Launches a generated kernel source (and its extra kernels) with the fusion calling convention:
     one argument block of 64-bit words = input tensor pointers, output pointers (one dummy word when
     there are none), numbers as double bits, the device RNG state pointers of graph-safe Philox
-    arguments (``rng_states``), then the workspace pointer when ``ks.ws_bytes``."""
-    if rng_states:
-        argbuf_t, argbuf_ws_t = arg_buffer_types(len(tensors), len(outs), len(numbers) + len(rng_states))
+    arguments (``rng_states``), then the workspace pointer when ``ks.ws_bytes``.
+
+    A symbolic region (``Plan.symbolic``; never column mode, so no workspace) extends the block with
+    ``tail``: first the runtime extents of the domain, one word per non-constant domain dim in domain
+    order (``Args.ext``), then the element strides of the tensor inputs, one word per load and domain dim
+    the load walks (``Args.str``; the order of ``Plan.sym["loads"]``).  The kernel narrows both to its
+    index type once and derives the contiguous output strides from the extents.  They are passed by
+    value, so a launch captured into a hipGraph keeps the sizes of its capture.  ``grid`` replaces the
+    main kernel's grid, which such a region sizes per call."""
+    if rng_states or (tail and argbuf_t is None):
+        argbuf_t, argbuf_ws_t = arg_buffer_types(len(tensors), len(outs),
+                                                 len(numbers) + len(rng_states or ()) + len(tail or ()))
     elif argbuf_t is None:
         argbuf_t, argbuf_ws_t = arg_buffer_types(len(tensors), len(outs), len(numbers))
     dev = (tensors or outs)[0].device
@@ -247,6 +329,9 @@ def launch(ks: cg.KernelSource, fns: list, tensors: list, outs: list, numbers: l
     for st in rng_states or ():
         buf[k] = st.data_ptr()
         k += 1
+    for x in tail or ():
+        buf[k] = x
+        k += 1
     ws = None
     from ..ops._lib import stream_ptr
 
@@ -256,7 +341,7 @@ def launch(ks: cg.KernelSource, fns: list, tensors: list, outs: list, numbers: l
         if ks.counters:
             buf = _with_counters(buf, _counters(ks.counters, dev))
 
-    launches = [(g, b) for _, g, b in ks.pre] + [(ks.grid, ks.block)] + [(g, b) for _, g, b in ks.extra]
+    launches = [(g, b) for _, g, b in ks.pre] + [(grid or ks.grid, ks.block)] + [(g, b) for _, g, b in ks.extra]
     for fn, (grid, block) in zip(fns, launches):
         rc = _lib().lta_rtc_launch(fn, grid[0], grid[1], grid[2], block[0], block[1], block[2], 0, stream_ptr(dev),
                                    ctypes.cast(buf, ctypes.c_void_p), ctypes.sizeof(buf))
@@ -414,7 +499,8 @@ def compile_source(ks: cg.KernelSource) -> bytes:
 def precompile(trace) -> int:
     """Generates and compiles (hiprtc, no GPU needed) the kernel of every hipfuse region of an
     execution trace for dense, 16-byte aligned inputs: an ahead-of-time build check (and disk-cache
-    warm-up) that surfaces codegen errors before a GPU run.  Returns the number of regions."""
+    warm-up) that surfaces codegen errors before a GPU run.  A symbolic region is compiled in the
+    variant its traced sizes imply (read without specialising them).  Returns the number of regions."""
     from ..core import dtypes as _dt
 
     fus = fusions(trace)
@@ -422,7 +508,7 @@ def precompile(trace) -> int:
         f = fb._call_ctx[fb.sym.name]
         targs = {}
         for p in (f.inputs[i] for i in f.tensor_pos):
-            shape = tuple(int(x) for x in p.shape)
+            shape = tuple(int(static_value(x)) for x in p.shape)
             targs[p.name] = cg.TensorArg(shape, cg._contig_strides(shape), _dt.to_torch_dtype(p.dtype), True)
         compile_source(cg.generate(f.plan, f.inputs, f.outputs, targs))  # one source: main + pre / extra kernels
     return len(fus)
@@ -720,7 +806,6 @@ def _fusion_pass(trace):
         if ncompute < 2 or not ex.get_fuel():
             new_bsyms.extend(original)
             continue
-        new_bsyms.extend(pre)
         post_after = post
         pre_names = {o.name for b in pre for o in b.flat_proxy_outs}
         produced = []
@@ -741,6 +826,11 @@ def _fusion_pass(trace):
                 if a.name not in pset and a.name not in seen:
                     seen.add(a.name)
                     inputs.append(a)
+        if plan.symbolic and not plan.bind(inputs, outputs):
+            # an extent no tensor input carries (e.g. a ``full`` of a symbolic shape alone): no region
+            new_bsyms.extend(original)
+            continue
+        new_bsyms.extend(pre)
         if not outputs:
             continue
         name = f"hipFusion{next(_counter)}"
@@ -787,8 +877,8 @@ def _trailing_views(group: list, internal_names: set, unstorable: set = frozense
 
 
 def _tensor_bytes(p) -> int:
-    n = p.numel
-    return int(n) * p.dtype.itemsize if isinstance(n, int) else 0
+    n = p.numel  # a symbolic size: its traced value (a cost heuristic, valid at any size; records nothing)
+    return int(static_value(n)) * p.dtype.itemsize if isinstance(n, int) else 0
 
 
 def _rematerialize_between_regions(items: list) -> dict:

@@ -8,8 +8,13 @@ The design is CDNA4-first rather than a translation:
   region's iteration **domain** (the largest elementwise shape).  Broadcasts, unit-dim
   reshapes/squeezes and keepdim reductions are therefore free: they only change maps.
   External tensors are read through per-domain-dim strides that are baked into the
-  source as constants (shapes are static in a trace; strides are specialised per call
-  signature), so every index computation is a multiply-shift, never a runtime divide.
+  source as constants (strides are specialised per call signature), so every index
+  computation is a multiply-shift, never a runtime divide.  A region with symbolic dims
+  (``cache="symbolic values"``; ``Plan.symbolic``) instead takes its non-constant extents and
+  its input strides as kernel arguments (size terms ``E<k>`` / ``S<k>``, ``_Sz``) and divides by
+  them at run time, unless every operand is dense over the whole domain; it bakes in only the
+  vector width, the index width and a stride / alignment class per load (``sym_call``), so
+  its code objects do not multiply with the sizes seen.  Pointwise and row mode only.
 * **Pointwise mode** (no reduction): a grid-stride loop in which every lane owns ``VEC``
   consecutive elements of the innermost dim -> 16-byte global loads/stores (8 x bf16),
   broadcast operands along the innermost dim are loaded once as scalars.
@@ -42,6 +47,7 @@ import torch
 
 from ..core.prims import PrimIDs
 from ..core.proxies import TensorProxy, NumberProxy, Proxy, pyval
+from ..core.symbolic import SymInt, known_constant, same_dim, static_value
 
 # -----------------------------------------------------------------------------------------
 # dtype tables
@@ -164,8 +170,32 @@ def _remap_amap(amap, f):
     return rm(amap)
 
 
+def _nz(s) -> bool:
+    """Is ``s`` a non-unit dim?  A symbolic dim counts as non-unit (the comparison records nothing: a map
+    that walks a dim whose extent turns out to be 1 is still right)."""
+    return static_value(s) != 1
+
+
 def _sq(shape):
-    return tuple(s for s in shape if s != 1)
+    return tuple(s for s in shape if _nz(s))
+
+
+def _seq(a, b) -> bool:
+    """Shape equality that holds at every admitted size (``core.symbolic.same_dim`` per dim)."""
+    return len(a) == len(b) and all(same_dim(x, y) for x, y in zip(a, b))
+
+
+def _any_symbolic(bsym) -> bool:
+    for p in (*bsym.flat_proxy_args, *bsym.flat_proxy_outs):
+        if isinstance(p, TensorProxy) and any(isinstance(d, SymInt) for d in p._shape):
+            return True
+    return False
+
+
+# prims a region with symbolic dims may hold (RESHAPE / SQUEEZE: unit dims only; reductions: trailing dims
+# of constant extent); everything else runs per op under cache="symbolic values"
+SYMBOLIC_OK = ELEMENTWISE | REDUCTIONS | {PrimIDs.BROADCAST_IN_DIM, PrimIDs.RESHAPE, PrimIDs.SQUEEZE, PrimIDs.TRANSPOSE,
+                                           PrimIDs.FULL, PrimIDs.UNIFORM_PHILOX}
 
 
 # -----------------------------------------------------------------------------------------
@@ -185,28 +215,32 @@ class Plan:
     # the region's closing scatter / index_put: {"node", "out", "a", "dim", "idx", "src"} (the region
     # takes no node after it)
     scatter: dict | None = None
+    # some domain dim is a SymInt (cache="symbolic values"): the kernel takes its extents and strides as
+    # arguments (``bind``); only SYMBOLIC_OK prims, no column mode, no conditional / indirect loads
+    symbolic: bool = False
+    sym: dict | None = None  # set by ``bind``: how a call's extents, strides and output shapes are found
 
     def copy(self) -> "Plan":
         return Plan(self.domain, self.red, self.colred, self.has_reduction, self.has_pad, list(self.nodes),
                     dict(self.maps), [dict(m) for m in self.arg_maps], set(self.post),
-                    dict(self.scatter) if self.scatter else None)
+                    dict(self.scatter) if self.scatter else None, self.symbolic)
 
     # --- maps ----------------------------------------------------------------------------
     def _identity(self, shape):
-        return tuple(i if s != 1 else None for i, s in enumerate(shape))
+        return tuple(i if _nz(s) else None for i, s in enumerate(shape))
 
     def _row_map(self, shape):
         """Map a row-shaped value (its non-unit dims == the non-unit row dims, in order)."""
         if self.domain is None or self.red == 0:
             return None
         nrow = len(self.domain) - self.red
-        rdims = [d for d in range(nrow) if self.domain[d] != 1]
-        nz = [i for i, s in enumerate(shape) if s != 1]
+        rdims = [d for d in range(nrow) if _nz(self.domain[d])]
+        nz = [i for i, s in enumerate(shape) if _nz(s)]
         if len(nz) != len(rdims):
             return None
         m = [None] * len(shape)
         for i, d in zip(nz, rdims):
-            if shape[i] != self.domain[d]:
+            if not same_dim(shape[i], self.domain[d]):
                 return None
             m[i] = d
         return tuple(m)
@@ -231,7 +265,7 @@ class Plan:
         shape = tuple(shape)
         if self.domain is None:
             return "new"
-        if shape == self.domain:
+        if _seq(shape, self.domain):
             return self._identity(shape)
         if self.colred:
             return self._col_map(shape)
@@ -266,7 +300,92 @@ class Plan:
                 raise NotFusible(f"dtype {t.dtype}")
 
     def _set_domain(self, shape):
-        self.domain = tuple(int(s) for s in shape)
+        # symbolic dims stay as they are: int() would specialise the program on their traced values
+        self.domain = tuple(s if isinstance(s, SymInt) else int(s) for s in shape)
+
+    def _admit_symbolic(self, bsym):
+        """A prim with symbolic dims joins (or a prim joins a region that has them): only the subset whose
+        sizes the kernels take at run time."""
+        if bsym.sym.id not in SYMBOLIC_OK:
+            raise NotFusible(f"{bsym.sym.id} in a symbolic region")
+        if self.colred or self.has_pad or self.scatter is not None:
+            raise NotFusible("symbolic dims in a column / pad / scatter region")
+        if not self.symbolic:
+            if any(_kind(m) is not None for am in self.arg_maps for m in am.values()):
+                raise NotFusible("symbolic dims in a region with affine / reshaped loads")
+            if any(b.sym.id not in SYMBOLIC_OK for b in self.nodes):
+                raise NotFusible("symbolic dims in a region with other prims")
+        for p in (*bsym.flat_proxy_args, *bsym.flat_proxy_outs):
+            if isinstance(p, TensorProxy) and any(isinstance(d, SymInt) and static_value(d) in (0, 1) for d in p._shape):
+                raise NotFusible("symbolic dim of extent 0 or 1")
+        self.symbolic = True
+
+    def bind(self, inputs, outputs) -> bool:
+        """Closes a symbolic region: finds, for every non-constant domain extent, a dim of a tensor input
+        that equals it at every admitted size (by value under the recorded equalities), the tensor dims
+        behind every runtime stride, and each output's shape in constants and bound extents
+        (``self.sym``).  False when something cannot be bound: the region is then not formed.  A region
+        whose symbolic dims are all pinned to constants becomes a static one."""
+        tins = [a for a in inputs if isinstance(a, TensorProxy)]
+        tidx = {a.name: i for i, a in enumerate(tins)}
+        nd = len(self.domain)
+        dom, ext_bind, slot = [], [], {}
+        for d, s in enumerate(self.domain):
+            c = known_constant(s)
+            if c is not None:
+                dom.append(c)
+                continue
+            hit = next(((i, j) for i, t in enumerate(tins) for j, x in enumerate(t.shape) if same_dim(x, s)), None)
+            if hit is None:
+                return False
+            dom.append(None)
+            slot[d] = len(ext_bind)
+            ext_bind.append(hit)
+        if not ext_bind:
+            self.domain, self.symbolic = tuple(dom), False
+            return True
+        if self.colred or any(x is None for x in dom[nd - self.red:]):
+            return False
+        loads, ident, nstr = {}, [], 0
+        for k, b in enumerate(self.nodes):
+            for pos, a in tensor_args(b):
+                if a.name in self.maps:
+                    continue
+                amap = self.arg_maps[k].get(pos)
+                if (a.name, amap) in loads:
+                    continue
+                if a.name not in tidx or amap is None or _kind(amap) is not None:
+                    return False
+                per = [[] for _ in range(nd)]
+                for i, d in enumerate(amap):
+                    if d is None or known_constant(a.shape[i]) == 1:
+                        continue
+                    if not same_dim(a.shape[i], self.domain[d]):
+                        return False  # the kernel walks this dim with the domain's extent
+                    per[d].append(i)
+                loads[(a.name, amap)] = (tidx[a.name], tuple(tuple(p) for p in per), nstr)
+                nstr += sum(1 for p in per if p)
+                ident.append(len(amap) == nd and all(p == [d] or (not p and dom[d] == 1) for d, p in enumerate(per)))
+        out_shapes, out_ident = [], []
+        for o in outputs:
+            m = self.maps.get(o.name)
+            if m is None or _kind(m) is not None:
+                return False
+            sh = []
+            for i, s in enumerate(o.shape):
+                c = known_constant(s)
+                if c is not None:
+                    sh.append(c)
+                elif m[i] in slot and same_dim(s, self.domain[m[i]]):
+                    sh.append(-1 - slot[m[i]])
+                else:
+                    return False
+            out_shapes.append(tuple(sh))
+            out_ident.append(len(m) == nd and all(x == i or (x is None and dom[i] == 1) for i, x in enumerate(m)))
+        items = [t.dtype.itemsize for t in tins] + [o.dtype.itemsize for o in outputs] + [1]
+        self.sym = dict(dom=tuple(dom), slot=slot, ext_bind=tuple(ext_bind), loads=loads, ident=tuple(ident), nstr=nstr,
+                        out_shapes=tuple(out_shapes), out_ident=tuple(out_ident), max_item=max(items))
+        return True
 
     # --- admission -----------------------------------------------------------------------
     def try_add(self, bsym) -> bool:
@@ -290,7 +409,9 @@ class Plan:
         self._check_dtype(*outs, *[a for a in bsym.flat_args if isinstance(a, TensorProxy)])
         for o in outs:
             if any(not isinstance(s, int) for s in o.shape):
-                raise NotFusible("symbolic shape")
+                raise NotFusible("non-integer shape")
+        if self.symbolic or _any_symbolic(bsym):
+            self._admit_symbolic(bsym)
         am: dict[int, tuple] = {}
         if sid in ELEMENTWISE:
             self._add_elementwise(bsym, am)
@@ -317,7 +438,7 @@ class Plan:
             out = bsym.output
             if self.domain is None:
                 self._set_domain(out.shape)
-            if tuple(out.shape) != self.domain:
+            if not _seq(tuple(out.shape), self.domain):
                 raise NotFusible("uniform_philox must span the iteration domain")
             self.maps[out.name] = self._identity(out.shape)
         elif sid == PrimIDs.FULL:
@@ -379,16 +500,16 @@ class Plan:
             om = self._map_for_shape(shape)
             if om is None or om == "new":
                 raise NotFusible("broadcast of pending value to non-domain shape")
-            self._resolve(a.name, tuple(om[bdims[i]] if a.shape[i] != 1 else None for i in range(len(a.shape))))
+            self._resolve(a.name, tuple(om[bdims[i]] if _nz(a.shape[i]) else None for i in range(len(a.shape))))
             self.maps[out.name] = om
             return
         if self._internal(a):
             amap = self.maps[a.name]
-            if self.domain is not None and shape != self.domain and tuple(a.shape) == self.domain and not self.has_reduction \
-                    and len(shape) >= len(self.domain):
+            if self.domain is not None and not _seq(shape, self.domain) and _seq(tuple(a.shape), self.domain) \
+                    and not self.has_reduction and len(shape) >= len(self.domain):
                 # domain upgrade: the whole (pointwise) region so far is re-indexed into the larger shape
                 for d, s in enumerate(self.domain):
-                    if s != 1 and shape[bdims[d]] != s:
+                    if _nz(s) and not same_dim(shape[bdims[d]], s):
                         raise NotFusible("bad upgrade")
                 def remap(mp):
                     return _remap_amap(mp, lambda x: bdims[x])
@@ -402,7 +523,7 @@ class Plan:
                 raise NotFusible("broadcast of internal to non-domain shape")
             # consistency: each non-broadcast dim of a keeps its domain dim
             for i, j in enumerate(bdims):
-                if a.shape[i] != 1 and amap[i] != om[j]:
+                if _nz(a.shape[i]) and amap[i] != om[j]:
                     raise NotFusible("inconsistent broadcast map")
             self.maps[out.name] = om
             return
@@ -412,7 +533,7 @@ class Plan:
             om = self._identity(shape)
         if om is None:
             raise NotFusible("broadcast of external to non-domain shape")
-        am[0] = tuple(om[bdims[i]] if a.shape[i] != 1 else None for i in range(len(a.shape)))
+        am[0] = tuple(om[bdims[i]] if _nz(a.shape[i]) else None for i in range(len(a.shape)))
         self.maps[out.name] = om
 
     def _add_transpose(self, bsym, am):
@@ -619,8 +740,8 @@ class Plan:
 
     def _add_unit_reshape(self, bsym, am):
         a, out = bsym.args[0], bsym.output
-        if _sq(a.shape) != _sq(out.shape):
-            if bsym.sym.id == PrimIDs.RESHAPE and not self._internal(a):
+        if not _seq(_sq(a.shape), _sq(out.shape)):
+            if bsym.sym.id == PrimIDs.RESHAPE and not self._internal(a) and not self.symbolic:
                 # a general reshape of an external input: read it as the reshaped tensor (a view
                 # when its strides allow, else an index decomposition)
                 om = self._ext_out_map(out, "reshape")
@@ -631,10 +752,10 @@ class Plan:
         if self._internal(a):
             if self.maps[a.name] is None:
                 raise NotFusible("unit reshape of a value whose index map is not known yet")
-            amap = [x for x, s in zip(self.maps[a.name], a.shape) if s != 1]
+            amap = [x for x, s in zip(self.maps[a.name], a.shape) if _nz(s)]
             om, k = [], 0
             for s in out.shape:
-                if s != 1:
+                if _nz(s):
                     om.append(amap[k])
                     k += 1
                 else:
@@ -647,10 +768,10 @@ class Plan:
             om = self._identity(out.shape)
         if om is None:
             raise NotFusible("reshape of external to non-domain shape")
-        onz = [x for x, s in zip(om, out.shape) if s != 1]
+        onz = [x for x, s in zip(om, out.shape) if _nz(s)]
         amap, k = [], 0
         for s in a.shape:
-            if s != 1:
+            if _nz(s):
                 amap.append(onz[k])
                 k += 1
             else:
@@ -666,24 +787,28 @@ class Plan:
         if not isinstance(a, TensorProxy) or a.ndim == 0 or not dims:
             raise NotFusible("reduction arg")
         if self._internal(a):
-            if tuple(a.shape) != self.domain or self.maps[a.name] != self._identity(a.shape):
+            if not _seq(tuple(a.shape), self.domain) or self.maps[a.name] != self._identity(a.shape):
                 raise NotFusible("reduction of non-domain value")
         else:
             if self.domain is None:
                 self._set_domain(a.shape)
-            elif tuple(a.shape) != self.domain:
+            elif not _seq(tuple(a.shape), self.domain):
                 raise NotFusible("reduction of non-domain external")
             am[0] = self._identity(a.shape)
         nd, k = len(self.domain), len(dims)
         if dims != tuple(range(nd - k, nd)) or self.colred:
-            if dims == tuple(range(k)) and k < nd:
+            if dims == tuple(range(k)) and k < nd and not self.symbolic:
                 self._add_column_reduction(bsym, a, k)
                 return
             raise NotFusible("non-trailing reduction")
         if self.red and self.red != k:
             raise NotFusible("different reduction dims")
-        rows = math.prod(self.domain[: nd - k])
-        R = math.prod(self.domain[nd - k:])
+        if self.symbolic and any(known_constant(s) is None for s in self.domain[nd - k:]):
+            # R, the lane partition and the reduction tree are compile-time: only the rows may vary
+            raise NotFusible("reduction over a symbolic extent")
+        # a symbolic row count: its traced value decides (a heuristic, valid at any size; records nothing)
+        rows = math.prod(static_value(s) for s in self.domain[: nd - k])
+        R = math.prod(static_value(s) for s in self.domain[nd - k:])
         if rows < 128 and R > 8192:
             raise NotFusible("too few rows for a row kernel")
         if bsym.sym.id == PrimIDs.SUM and bsym.kwargs.get("output_dtype") not in (None, bsym.output.dtype):
@@ -852,6 +977,65 @@ def _contig_strides(shape):
     return tuple(reversed(st))
 
 
+class _Sz:
+    """A size term the kernel only knows at run time: a C expression of the index type (an extent slot
+    ``E<k>``, a stride slot ``S<k>``, or a product of those and literals).  The other kind of size term is a
+    Python int, printed as a literal (``_t``); products mix the two."""
+
+    def __init__(self, expr: str):
+        self.expr = expr
+
+    def __mul__(self, o):
+        if isinstance(o, _Sz):
+            return _Sz(f"{self.expr} * {o.expr}")
+        return self if o == 1 else _Sz(f"{self.expr} * {o}u")
+
+    __rmul__ = __mul__
+
+    def __str__(self):
+        return f"({self.expr})" if " " in self.expr else self.expr
+
+
+def _t(x) -> str:
+    """A size term in source: the literal of an int, the expression of a runtime term."""
+    return str(x) if isinstance(x, _Sz) else f"{x}u"
+
+
+def sym_grid(mode: tuple, D: list, red: int) -> int:
+    """Workgroups of a symbolic region's kernel for this call's domain ``D``; ``mode`` is
+    ``KernelSource.sym_mode``: ("pointwise", vector width) or ("row", rows per workgroup)."""
+    if mode[0] == "pointwise":
+        nvec = math.prod(D) // mode[1]
+        return max(1, min((nvec + 255) // 256, 4096 * 2))
+    return max(1, (math.prod(D[:len(D) - red]) + mode[1] - 1) // mode[1])
+
+
+def sym_call(plan: Plan, meta: list):
+    """One call of a symbolic region.  ``meta``: (shape, strides, 16-byte aligned) of every tensor input.
+    Returns (variant key, extents, stride words, domain): the key holds everything the source bakes in
+    (vector width, 64-bit indices, and per load the innermost-stride class 0 / 1 / other, whether every outer
+    stride is a multiple of the vector width, and whether the load is dense over the whole domain), so the
+    number of code objects never grows with the sizes seen."""
+    sym = plan.sym
+    ext = [meta[i][0][j] for i, j in sym["ext_bind"]]
+    D = [ext[sym["slot"][d]] if c is None else c for d, c in enumerate(sym["dom"])]
+    nd = len(D)
+    vec = 1
+    for v in ((8, 4, 2) if sym["max_item"] <= 4 else (4, 2)):
+        if D[-1] % v == 0:
+            vec = v
+            break
+    big = math.prod(D) >= 2**31 or any(sum((s - 1) * st for s, st in zip(sh, strd)) >= 2**31 for sh, strd, _ in meta)
+    words, classes = [], []
+    for (ti, per, _), ident in zip(sym["loads"].values(), sym["ident"]):
+        sh, strd, _ = meta[ti]
+        sv = [sum(strd[i] for i in p) for p in per]
+        words += [sv[d] for d in range(nd) if per[d]]
+        dense = ident and all(sv[d] == math.prod(D[d + 1:]) for d in range(nd) if per[d] and D[d] != 1)
+        classes.append((min(sv[-1], 2), all(x % vec == 0 for x in sv[:-1]), dense))
+    return (vec, big, tuple(m[2] for m in meta), tuple(classes)), ext, words, D
+
+
 _VALUE_ID = re.compile(r"\b([vr])_([A-Za-z_]\w*)")
 
 
@@ -924,8 +1108,10 @@ def generate(plan: Plan, inputs: list, outputs: list, targs: dict, kernel_prefix
     h = hashlib.sha1(src.encode()).hexdigest()[:16]
     name = f"{kernel_prefix}_{h}"
     src = src.replace("__KERNEL_NAME__", name)
-    return KernelSource(name, src, grid, block, vec, mode, extra=g.extra, ws_bytes=g.ws_bytes, pre=g.pre,
-                        counters=g.counters)
+    ks = KernelSource(name, src, grid, block, vec, mode, extra=g.extra, ws_bytes=g.ws_bytes, pre=g.pre,
+                      counters=g.counters)
+    ks.sym_mode = g.sym_mode  # symbolic regions: how the host sizes the grid of each call (sym_grid)
+    return ks
 
 
 class _Gen:
@@ -937,6 +1123,16 @@ class _Gen:
         self.outputs = outputs
         self.targs = targs
         self.D = plan.domain if plan.domain is not None else ()
+        # a symbolic region (Plan.bind): runtime extents are size terms E<k>; what the source bakes in comes
+        # from this call's tensors through sym_call, the same function the host keys its variants with
+        self.sym = plan.sym if plan.symbolic else None
+        if self.sym:
+            tins = [a for a in inputs if isinstance(a, TensorProxy)]
+            self.sym_key, _, _, self.Dc = sym_call(plan, [(targs[a.name].shape, targs[a.name].strides,
+                                                           targs[a.name].align16) for a in tins])
+            self.D = tuple(_Sz(f"E{self.sym['slot'][d]}") if c is None else c for d, c in enumerate(self.sym["dom"]))
+        self.sym_mode = None
+        self.flat_all = False  # symbolic pointwise region of dense identity operands: no index decomposition
         self.nd = len(self.D)
         self.red = plan.red
         self.colred = plan.colred
@@ -1020,6 +1216,13 @@ class _Gen:
     def build(self):
         self._analyse()
         D, nd = self.D, self.nd
+        if self.sym:
+            # the vector width (the constant innermost extent, else this call's by divisibility) and the
+            # index width are baked per variant; numel is a runtime term
+            self.vec, big = self.sym_key[0], self.sym_key[1]
+            self.IT = "unsigned long long" if big else "unsigned"
+            numel = math.prod(D)
+            return self._build_row(numel) if self.red else self._build_pointwise(numel)
         numel = math.prod(D) if D else 1
         # choose VEC along the innermost domain dim
         inner = D[-1] if nd else 1
@@ -1054,6 +1257,10 @@ class _Gen:
             fields.append("void* ws;")
             if self.counters:
                 fields.append("unsigned* cnt;")
+        if self.sym:
+            fields.append(f"unsigned long long ext[{len(self.sym['ext_bind'])}];")
+            if self.sym["nstr"]:
+                fields.append(f"unsigned long long str[{self.sym['nstr']}];")
         return "struct Args { " + " ".join(fields) + " };"
 
     def _ptr(self, t: TensorProxy, is_out: bool) -> str:
@@ -1350,6 +1557,22 @@ class _Gen:
         if kind == "gather":
             return self._emit_gather_load(a, amap, nm, out, indent)
         ta = self.targs[a.name]
+        if self.sym:
+            # strides are runtime terms S<k> (one per domain dim the input walks), except the innermost
+            # one when its class is 0 or 1; the variant's classes decide the vector load
+            n = list(self.sym["loads"]).index((a.name, amap))
+            _, per, k = self.sym["loads"][(a.name, amap)]
+            inner, outer_ok, dense = self.sym_key[3][n]
+            st = []
+            for d in range(self.nd):
+                if not per[d]:
+                    st.append(0)
+                    continue
+                st.append(inner if d == self.nd - 1 and inner < 2 else _Sz(f"S{k}"))
+                k += 1
+            # a load that is dense over the whole domain of a pointwise region needs no index: the flat one is it
+            return self._emit_affine_load(a, ta, st, 0, None, nm, vec_scope, out, indent, outer_ok=outer_ok,
+                                          flat=dense and not self.red and vec_scope)
         if kind == "reshape":
             vs = _view_strides(ta.shape, ta.strides, amap[2])
             if vs is None:
@@ -1361,19 +1584,22 @@ class _Gen:
             c0 = sum(int(b) * int(st) for b, st in zip(amap[2], ta.strides))
         self._emit_affine_load(a, ta, self._dstrides(ta, amap), c0, None, nm, vec_scope, out, indent)
 
-    def _emit_affine_load(self, a, ta, st, c0, guard, nm, vec_scope, out, indent, fill=0):
+    def _emit_affine_load(self, a, ta, st, c0, guard, nm, vec_scope, out, indent, fill=0, outer_ok=None, flat=False):
         """Load ``a`` at element offset sum(i_d * st[d]) + c0 (c0 may be negative: wrap-around
         index arithmetic, only evaluated where the true offset is in range); with ``guard`` (a
-        per-vector condition) the load is skipped and 0 is used where it is false."""
+        per-vector condition) the load is skipped and 0 is used where it is false.  The strides are
+        size terms; ``outer_ok`` says whether runtime outer strides are multiples of the vector width."""
         ct, sty = _CTYPE[a.dtype], _STYPE[a.dtype]
         ptr = self._ptr(a, False)
         for d in range(self.nd):
-            if st[d] and f"i{d}" not in self.idx_avail:
+            if st[d] and f"i{d}" not in self.idx_avail and not flat:
                 raise NotFusible(f"codegen: index i{d} not available for load of {a.name}")
-        terms = [f"(({self.IT})i{d} * {st[d]}u)" for d in range(self.nd) if st[d]]
+        terms = [f"(({self.IT})i{d} * {_t(st[d])})" for d in range(self.nd) if st[d]]
         if c0:
             terms.append(f"({self.IT})({c0}ll)")
         off = " + ".join(terms) or "0"
+        if flat:
+            off = "e"  # dense over the whole domain: the flat index is the offset
         if not vec_scope:
             assert guard is None
             out.append(f"{indent}const {ct} {nm} = {_load_conv(a.dtype, f'{ptr}[{off}]')};")
@@ -1389,7 +1615,9 @@ class _Gen:
             out.append(f"{indent}#pragma unroll")
             out.append(f"{indent}for (int j = 0; j < {V}; ++j) {nm}[j] = {nm}_s;")
             return
-        vec_ok = V > 1 and sl == 1 and ta.align16 and all(st[d] % V == 0 for d in range(last)) and c0 % V == 0
+        if outer_ok is None:
+            outer_ok = all(st[d] % V == 0 for d in range(last))
+        vec_ok = V > 1 and sl == 1 and ta.align16 and outer_ok and c0 % V == 0
         out.append(f"{indent}{ct} {nm}[{V}];")
         if guard:
             out.append(f"{indent}#pragma unroll")
@@ -1403,7 +1631,7 @@ class _Gen:
         else:
             out.append(f"{indent}{{")
             out.append(f"{indent}#pragma unroll")
-            out.append(f"{indent}for (int j = 0; j < {V}; ++j) {nm}[j] = {_load_conv(a.dtype, f'{ptr}[({off}) + ({self.IT})j * {sl}u]')}; }}")
+            out.append(f"{indent}for (int j = 0; j < {V}; ++j) {nm}[j] = {_load_conv(a.dtype, f'{ptr}[({off}) + ({self.IT})j * {_t(sl)}]')}; }}")
 
     def _emit_cat_load(self, a, amap, nm, out, indent):
         """One piece of a concatenation.  When every vector lies inside one piece (the cat dim is
@@ -1498,10 +1726,13 @@ class _Gen:
     def _out_strides(self, o):
         """Per-domain-dim strides of a (contiguous) output plus its guard dims."""
         m = self.p.maps[o.name]
-        cst = _contig_strides(tuple(o.shape))
+        shape = tuple(o.shape)
+        if self.sym:  # constants and bound extents: the strides are derived in the kernel from the extents
+            shape = tuple(s if s >= 0 else _Sz(f"E{-1 - s}") for s in self.sym["out_shapes"][self.out_index[o.name]])
+        cst = _contig_strides(shape)
         st = [0] * self.nd
         for i, d in enumerate(m):
-            if d is not None and o.shape[i] != 1:
+            if d is not None and shape[i] != 1:
                 st[d] = cst[i]
         guard = [d for d in range(self.nd) if self.D[d] != 1 and st[d] == 0]
         return st, guard
@@ -1510,7 +1741,9 @@ class _Gen:
         st, guard = self._out_strides(o)
         ptr = self._ptr(o, True)
         val = f"v_{o.name}" if (vec_scope and self.dep.get(o.name, True)) else f"r_{o.name}"
-        off = " + ".join(f"(({self.IT})i{d} * {st[d]}u)" for d in range(self.nd) if st[d]) or "0"
+        off = " + ".join(f"(({self.IT})i{d} * {_t(st[d])})" for d in range(self.nd) if st[d]) or "0"
+        if self.sym and not self.red and self.sym["out_ident"][self.out_index[o.name]]:
+            off = "e"  # a pointwise region's identity-mapped (contiguous) output: the flat index is the offset
         last = self.nd - 1
         if vec_scope:
             g = [f"i{d} == 0" for d in guard if d != last]
@@ -1543,7 +1776,7 @@ class _Gen:
             src = f"{val}[j]" if val.startswith("v_") else val
             out.append(f"{indent}{pre}{{")
             out.append(f"{indent}#pragma unroll")
-            out.append(f"{indent}for (int j = 0; j < {V}; ++j) {ptr}[({off}) + ({self.IT})j * {sl}u] = {_store_conv(o.dtype, src)}; }}")
+            out.append(f"{indent}for (int j = 0; j < {V}; ++j) {ptr}[({off}) + ({self.IT})j * {_t(sl)}] = {_store_conv(o.dtype, src)}; }}")
 
     def _decompose(self, var: str, dims: list, out: list, indent: str):
         """i{d} = index of domain dim d from the flat index ``var`` over ``dims`` (row-major)."""
@@ -1553,9 +1786,9 @@ class _Gen:
             if s == 1:
                 out.append(f"{indent}const {self.IT} i{d} = 0;")
             elif rem == 1:
-                out.append(f"{indent}const {self.IT} i{d} = {var} % {s}u;")
+                out.append(f"{indent}const {self.IT} i{d} = {var} % {_t(s)};")
             else:
-                out.append(f"{indent}const {self.IT} i{d} = ({var} / {rem}u) % {s}u;")
+                out.append(f"{indent}const {self.IT} i{d} = ({var} / {_t(rem)}) % {_t(s)};")
             rem *= s
             self.idx_avail.add(f"i{d}")
 
@@ -1564,15 +1797,25 @@ class _Gen:
         self.load_names, self.loaded, self._scope_id = {}, set(), "vec"
         self.idx_avail = set()
         body: list[str] = []
-        nvec = numel // V
         block = 256
-        grid = max(1, min((nvec + block - 1) // block, 4096 * 2))
         ind = "    "
-        body.append(f"  for ({IT} v = ({IT})blockIdx.x * {block}u + threadIdx.x; v < {nvec}u; v += ({IT})gridDim.x * {block}u) {{")
+        if self.sym:
+            # a runtime vector count (the host sizes the grid per call, ``sym_grid``); operands that are all
+            # dense over the whole domain are addressed by the flat index alone
+            self.sym_mode = ("pointwise", V)
+            grid = sym_grid(self.sym_mode, self.Dc, 0)
+            self.flat_all = all(self.sym["out_ident"]) and all(c[2] for c in self.sym_key[3])
+            body.append(f"  const {IT} nvec = {numel} / {V}u;")
+            body.append(f"  for ({IT} v = ({IT})blockIdx.x * {block}u + threadIdx.x; v < nvec; v += ({IT})gridDim.x * {block}u) {{")
+        else:
+            nvec = numel // V
+            grid = max(1, min((nvec + block - 1) // block, 4096 * 2))
+            body.append(f"  for ({IT} v = ({IT})blockIdx.x * {block}u + threadIdx.x; v < {nvec}u; v += ({IT})gridDim.x * {block}u) {{")
         body.append(f"{ind}const {IT} e = v * {V}u;")
         self.flat_index = "((unsigned long long)e + (unsigned long long)j)"
         self.flat_base4 = "e" if V % 4 == 0 else None
-        self._decompose("e", list(range(self.nd)), body, ind)
+        if not self.flat_all:
+            self._decompose("e", list(range(self.nd)), body, ind)
         emitted: set = set()
         # referencing builds the load-name table lazily; pre-populate by a dry run over all nodes
         for k, b in enumerate(self.p.nodes):
@@ -1677,7 +1920,11 @@ class _Gen:
         RPB = 256 // T
         W = max(1, T // 64)
         block = 256
-        grid = (rows + RPB - 1) // RPB
+        if self.sym:  # rows is a runtime term: R, T, RPB, the lane partition and the reduction tree are not
+            self.sym_mode = ("row", RPB)
+            grid = sym_grid(self.sym_mode, self.Dc, red)
+        else:
+            grid = (rows + RPB - 1) // RPB
         self.load_names, self.loaded = {}, set()
         self.idx_avail = set()
         self.flat_index = f"((unsigned long long)rowc * {R}ull + (unsigned long long)c + (unsigned long long)j)"
@@ -1688,7 +1935,7 @@ class _Gen:
         body: list[str] = []
         body.append(f"  const unsigned lane = threadIdx.x % {T}u;")
         body.append(f"  const {IT} row = ({IT})blockIdx.x * {RPB}u + threadIdx.x / {T}u;")
-        body.append(f"  const bool rvalid = row < {rows}u;")
+        body.append(f"  const bool rvalid = row < {_t(rows)};")
         body.append(f"  const {IT} rowc = rvalid ? row : 0u;")
         if W > 1:
             body.append("  const unsigned wv = threadIdx.x / 64u;")
@@ -2243,4 +2490,11 @@ class _Gen:
         # graph-safe Philox state: read once per thread (the outputs' stores could alias it for the compiler)
         for ri in range(self.n_rng):
             head.append(f"  const long long rng_seed{ri} = A.rng[{ri}][0], rng_base{ri} = A.rng[{ri}][1];")
+        if self.sym:  # the runtime extents and strides, narrowed to the index type once
+            used = "\n".join(body)
+            for k in range(len(self.sym["ext_bind"])):
+                head.append(f"  const {self.IT} E{k} = ({self.IT})A.ext[{k}];")
+            for k in range(self.sym["nstr"]):
+                if re.search(rf"\bS{k}\b", used):
+                    head.append(f"  const {self.IT} S{k} = ({self.IT})A.str[{k}];")
         return "\n".join(head + body + ["}"]) + "\n"
