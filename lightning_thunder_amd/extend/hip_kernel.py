@@ -97,6 +97,10 @@ class HipKernel:
 
         grid = tuple(grid) + (1,) * (3 - len(grid))
         block = tuple(block) + (1,) * (3 - len(block))
+        for kind, a in zip(self.signature, args):
+            # a host pointer would be dereferenced on the GPU: an illegal access that poisons the whole process
+            if kind == "ptr" and isinstance(a, torch.Tensor) and not a.is_cuda:
+                raise ValueError(f"{self.name}: a pointer argument is a {a.device.type} tensor, not GPU memory")
         if stream is None:
             dev = next((a.device for a in args if isinstance(a, torch.Tensor) and a.is_cuda), None)
             stream = torch.cuda.current_stream(dev)

@@ -1,5 +1,6 @@
 """Shared assertions of the kernel-against-fp64 batteries (test_decode_kernels.py, test_train_row_kernels.py,
-test_attention_kernels.py) and the mirror of the attention kernels' dropout hash.
+test_attention_kernels.py, test_gemm_kernels.py), the mirror of the attention kernels' dropout hash, and the
+guard / poison buffers that show a kernel writing outside its result or reading outside its operands.
 
 Tolerance of every rounded output, per element:  ulp(T) * |ref64| + 8 * e32 + floor.
 ``ulp`` is the spacing of T at 1 (2^-8 bf16, 2^-10 fp16, 2^-23 fp32): the single rounding of the
@@ -93,3 +94,49 @@ def bits_equal(a, b):
         return False
     it = _INT_VIEW[a.dtype]
     return torch.equal(a.contiguous().view(it), b.contiguous().view(it))
+
+
+# ------------------------------------------------------------------------------------------------
+# guards and poison: results as views of sentinel-filled buffers, operands as views of NaN-filled ones
+# ------------------------------------------------------------------------------------------------
+SENTINEL = 0x5A3C  # int16 pattern of every 16-bit word around a guarded result (a finite bf16, 1.3e16)
+
+
+def guarded(shape, device, pads=None, dtype=BF16):
+    """(buf, view): ``view`` is a 16-bit tensor of ``shape``, the leading corner of the int16 buffer ``buf``
+    whose every word is SENTINEL.  ``pads`` are the extra elements per dim (default: 8 more rows and a
+    pitch 64 elements longer on the last two dims, nothing on the leading ones)."""
+    assert dtype in (BF16, F16)
+    shape = tuple(shape)
+    if pads is None:
+        pads = (0,) * (len(shape) - 2) + (8, 64)
+    assert len(pads) == len(shape)
+    buf = torch.full(tuple(s + p for s, p in zip(shape, pads)), SENTINEL, dtype=torch.int16, device=device)
+    return buf, buf.view(dtype)[tuple(slice(0, s) for s in shape)]
+
+
+def assert_guard_intact(buf, shape, what=""):
+    """Every word of ``buf`` (from :func:`guarded`) outside its leading ``shape`` corner is still SENTINEL."""
+    rest = buf.clone()
+    rest[tuple(slice(0, s) for s in shape)] = SENTINEL
+    bad = rest != SENTINEL
+    n = int(bad.sum().item())
+    assert n == 0, (f"{what}: {n} words outside the {tuple(shape)} result were overwritten, the first at "
+                    f"{tuple(int(i) for i in bad.nonzero()[0])}")
+
+
+def nan_padded(t, pad_rows=8, pad_cols=8):
+    """A view equal to ``t`` (floating point, >= 2-D) inside a NaN-filled buffer: ``pad_rows`` more rows and
+    a pitch of the columns rounded up to 8 elements plus ``pad_cols`` on the last two dims (16-byte aligned
+    rows for 16-bit types).  A kernel that consumes a padding column or a row past the end yields NaN."""
+    assert t.dim() >= 2 and t.is_floating_point() and pad_cols % 8 == 0
+    *lead, R, C = t.shape
+    buf = torch.full((*lead, R + pad_rows, (C + 7) // 8 * 8 + pad_cols), float("nan"), dtype=t.dtype, device=t.device)
+    view = buf[..., :R, :C]
+    view.copy_(t)
+    return view
+
+
+def poison(t):
+    """Fill a scratch buffer with NaN in place (stale contents that nothing may consume)."""
+    return t.fill_(float("nan"))

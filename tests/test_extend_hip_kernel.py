@@ -60,6 +60,16 @@ def test_pack_natural_alignment():
         HipKernel("", "f", ("float",))
 
 
+def test_cpu_tensor_is_refused_before_the_launch():
+    """A host tensor as a pointer argument raises; it is never handed to a kernel (on a machine with a GPU
+    the launch would dereference host memory on the device: an illegal access)."""
+    k = HipKernel(SCALE_ADD, "scale_add", ("ptr", "ptr", "ptr", "f32", "i64"))
+    x = torch.randn(16)
+    with pytest.raises(ValueError, match="cpu tensor"):
+        k((1,), (256,), x, x, torch.empty_like(x), 1.5, 16)
+    assert k._fn is None  # nothing was compiled or loaded for it
+
+
 @pytest.mark.skipif(not os.path.exists(LIB), reason="native library not built")
 def test_compiles_for_gfx950_without_gpu():
     k = HipKernel(SILU, "silu_bf16", ("ptr", "ptr", "i64"), defines={"TILE": 4})
@@ -116,7 +126,7 @@ def test_registered_op_traces_and_replaces_torch_function():
     try:
         jf(x)
     except Exception:
-        pass  # no GPU: the kernel launch fails, the traces exist
+        pass  # CPU tensors: the kernel refuses them before any launch, the traces exist
     fw = str(thunder.last_traces(jf)[-1])
     assert "user_silu" in fw
 
