@@ -30,7 +30,11 @@ import time
 import torch
 
 
-def _build(model_name: str, max_seq: int, device, n_layer=None):
+# --kv-cache-dtype: "model" keeps the cache in the model's dtype, "fp8" stores unscaled e4m3 (half the bytes)
+KV_CACHE_DTYPES = {"model": torch.bfloat16, "fp8": torch.float8_e4m3fn}
+
+
+def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model"):
     from ..models.litgpt import GPT, Config, init_weights
 
     kw = {} if n_layer is None else {"n_layer": n_layer}
@@ -42,7 +46,7 @@ def _build(model_name: str, max_seq: int, device, n_layer=None):
     init_weights(model)
     model.requires_grad_(False)
     model.eval()
-    model.set_kv_cache(1, max_seq, device=device, dtype=torch.bfloat16)
+    model.set_kv_cache(1, max_seq, device=device, dtype=KV_CACHE_DTYPES[kv_cache_dtype])
     return model, cfg
 
 
@@ -86,7 +90,7 @@ def run(mode: str, args) -> dict:
         def once():
             return gm.generate(prompt, **kw)
     else:
-        model, cfg = _build(args.model, args.prompt_len + args.new_tokens + 8, device, args.n_layer)
+        model, cfg = _build(args.model, args.prompt_len + args.new_tokens + 8, device, args.n_layer, args.kv_cache_dtype)
         prompt = torch.randint(0, cfg.vocab_size, (1, args.prompt_len), device=device)
         if mode == "eager":
             fwd = model
@@ -130,6 +134,7 @@ def run(mode: str, args) -> dict:
         "mode": mode, "value": round(ms, 2), "unit": "ms", "higher_is_better": False,
         "ms_per_token": round(ms / args.new_tokens, 3), "first_call_s": round(first, 2),
         "prompt_len": args.prompt_len, "new_tokens": args.new_tokens,
+        "kv_cache_dtype": "model" if mode.startswith("hf_") else args.kv_cache_dtype,
         "dtype": "mxfp4 weights, bf16 activations" if mode.endswith("mxfp4") else "bf16",
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
         "reference_ms": {"thunder+cudagraphs (1xH100)": 542, "eager (1xH100)": 1493},
@@ -161,6 +166,8 @@ def main(argv=None):
     p.add_argument("--temperature", type=float, default=0.0, help="> 0: sample (LitGPT modes only) instead of greedy")
     p.add_argument("--top-k", type=int, default=None)
     p.add_argument("--top-p", type=float, default=None)
+    p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_DTYPES), default="model",
+                   help="LitGPT modes: 'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes)")
     p.add_argument("--seed", type=int, default=0, help="torch.manual_seed before every sampled generation")
     args = p.parse_args(argv)
     results = []

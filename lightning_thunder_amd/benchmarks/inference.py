@@ -31,6 +31,10 @@ def _percentile(xs, q):
     return s[min(len(s) - 1, int(round(q * (len(s) - 1))))]
 
 
+# --kv-cache-dtype: "model" keeps the cache in the model's dtype, "fp8" stores unscaled e4m3 (half the bytes)
+KV_CACHE_DTYPES = {"model": torch.bfloat16, "fp8": torch.float8_e4m3fn}
+
+
 def _build(args, device):
     from ..models.litgpt import GPT, Config, init_weights
 
@@ -44,7 +48,7 @@ def _build(args, device):
     model.requires_grad_(False)
     model.eval()
     model.set_kv_cache(args.batch_size, args.input_length + args.output_length + 8, device=device,
-                       dtype=torch.bfloat16)
+                       dtype=KV_CACHE_DTYPES[args.kv_cache_dtype])
     return model, cfg
 
 
@@ -66,6 +70,8 @@ def run(mode: str, args) -> dict:
     from ..ops.sampling import argmax_last
 
     device = torch.device("cuda", 0)
+    torch.empty(1, device=device)  # the allocator exists from the first allocation on
+    torch.cuda.reset_peak_memory_stats(device)
     model, cfg = _build(args, device)
     fwd = _forward_for(mode, model)
     gen = torch.Generator(device).manual_seed(1)
@@ -117,7 +123,12 @@ def run(mode: str, args) -> dict:
         "latency_ms_per_request": round(1e3 * statistics.mean(totals), 2),
         "first_call_s": round(first, 2),
         "batch_size": B, "input_length": args.input_length, "output_length": n_out,
-        "dtype": "bf16", "data": "synthetic prompt, random-init weights", "n_gpus": 1,
+        "dtype": "bf16", "kv_cache_dtype": args.kv_cache_dtype,
+        "kv_cache_gib": round(sum(c.numel() * c.element_size() for b in model.transformer.h
+                                  for c in (b.attn.kv_cache.k, b.attn.kv_cache.v)) / 2 ** 30, 3),
+        "memory_allocated_gib": round(torch.cuda.memory_allocated(device) / 2 ** 30, 3),  # held after the last step
+        "max_memory_allocated_gib": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 3),
+        "data": "synthetic prompt, random-init weights", "n_gpus": 1,
     }
 
 
@@ -131,6 +142,8 @@ def main(argv=None):
     p.add_argument("--warmup-iterations", type=int, default=2)
     p.add_argument("--modes", default="eager,thunder,hipgraph")
     p.add_argument("--n-layer", type=int, default=None, help="debug only")
+    p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_DTYPES), default="model",
+                   help="'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes)")
     args = p.parse_args(argv)
     if args.output_length < 1:
         p.error("--output-length must be >= 1")

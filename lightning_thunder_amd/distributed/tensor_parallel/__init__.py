@@ -162,7 +162,8 @@ class TensorParallelTransform(Transform):
                     pm.config = replace(cfg, n_head=nh // world, n_query_groups=ng // world)
                     kv = getattr(pm, "kv_cache", None)
                     if kv is not None and hasattr(kv, "k") and kv.k.shape[1] == ng:
-                        # a cache allocated before sharding holds every kv group: keep this rank's
+                        # a cache allocated before sharding holds every kv group: keep this rank's, in the
+                        # cache's own storage dtype (uint8 for an e4m3 cache: slicing, never a cast)
                         kv.k = kv.k[:, rank * (ng // world):(rank + 1) * (ng // world)].contiguous()
                         kv.v = kv.v[:, rank * (ng // world):(rank + 1) * (ng // world)].contiguous()
                     head_done.update((qkv_name, proj_name))

@@ -912,13 +912,23 @@ def _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_
     return TensorProxy(like=qkv, shape=(B, n_head, T, head_size)), TensorProxy(like=kc), TensorProxy(like=vc)
 
 
+def _e4m3_bytes(t):
+    """The stored form of an unscaled e4m3 KV cache row: saturate, round to nearest even, as bytes."""
+    return t.clamp(-_E4M3_MAX, _E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
 def _qkv_rope_cache_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
     from ..ops.fused import qkv_rope_cache_fwd, qkv_rope_cache_supported, qkv_rope_fwd
 
-    if qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size):
+    kv8 = kc.dtype == torch.uint8  # unscaled e4m3 caches (models/litgpt.py KVCache)
+    if kv8 != (vc.dtype == torch.uint8):
+        raise ValueError("hip_qkv_rope_cache: one of the two caches is uint8 (e4m3), the other is not")
+    if qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size, rope_n):
         return qkv_rope_cache_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos)
     q, k, v = qkv_rope_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
     pos = pos if pos.dtype == torch.int64 else pos.long()  # index_copy_ takes int64 indices only
+    if kv8:
+        k, v = _e4m3_bytes(k), _e4m3_bytes(v)
     return q, kc.index_copy_(2, pos, k), vc.index_copy_(2, pos, v)
 
 
@@ -927,11 +937,59 @@ hip_qkv_rope_cache = ex.register_operator("hip_qkv_rope_cache", meta=_qkv_rope_c
 hip_qkv_rope_cache.written_args = (7, 8)  # kc, vc; qkv/cos/sin/pos are only read
 
 
+_E4M3_MAX = 448.0
+
+
+def _kv8_fusion_off() -> bool:
+    """LTA_KV8_FUSION=0 keeps the e4m3 KV cache's quantising writes and dequantising reads as the
+    separate operations the model spells (A/B against the two fused kernels)."""
+    return os.environ.get("LTA_KV8_FUSION", "1") == "0"
+
+
+def _only_tensor_arg(b, rest=0):
+    """``b``'s tensor operand when it is called as ``op(tensor, <rest literals>)`` with no keywords."""
+    if b.kwargs or len(b.args) != 1 + rest or not isinstance(b.args[0], TensorProxy):
+        return None
+    return b.args[0]
+
+
+def _e4m3_quantise_chain(rw, t):
+    """``[clamp, to, view]`` positions when ``t`` is read once, by ``clamp(t, -448.0, 448.0)``, whose
+    result is read once by ``to(float8_e4m3fn)``, whose result is read once by ``view(uint8)``; the
+    uint8 tensor is the last one's output.  None for anything else: other bounds, no clamp or another
+    fp8 format would give other bytes than the kernel's saturating e4m3 conversion."""
+    chain = []
+    for names, rest in ((("clamp", "torch_clamp"), (-_E4M3_MAX, _E4M3_MAX)),
+                        (("to", "torch_to"), (torch.float8_e4m3fn,)),
+                        (("view", "torch_view"), (torch.uint8,))):
+        if rw.uses(t) != 1:
+            return None
+        (j,) = rw.consumers(t)
+        b = rw.bsyms[j]
+        if rw.touched(j) or b.sym.name not in names or _only_tensor_arg(b, len(rest)) is not t:
+            return None
+        for got, want in zip(b.args[1:], rest):
+            if isinstance(want, float):
+                if isinstance(got, bool) or not isinstance(got, (int, float)) or float(got) != want:
+                    return None
+            elif got is not want:
+                return None
+        if not isinstance(b.output, TensorProxy):
+            return None
+        chain.append(j)
+        t = b.output
+    return chain
+
+
 def _fuse_kv_cache_writes(trace):
     """``q, k, v = hip_qkv_rope(...); kc = index_copy_inplace(cache_k, 2, pos, k);
     vc = index_copy_inplace(cache_v, 2, pos, v)`` (k, v used nowhere else) ->
     ``q, kc, vc = hip_qkv_rope_cache(..., cache_k, cache_v, pos)``: the rotated keys and the values
-    are stored straight into the static caches by the RoPE kernel (two launches fewer per layer)."""
+    are stored straight into the static caches by the RoPE kernel (two launches fewer per layer).
+
+    With uint8 (unscaled e4m3) caches k and v reach their write through
+    ``clamp(-448, 448) -> to(float8_e4m3fn) -> view(uint8)``, every link read once; the kernel
+    converts in the same launch (eight launches fewer per layer)."""
     rw = Rewrite(trace, ex)
     for i, b in enumerate(rw.bsyms):
         if b.sym is not hip_qkv_rope:
@@ -940,16 +998,25 @@ def _fuse_kv_cache_writes(trace):
         if rw.uses(k) != 1 or rw.uses(v) != 1:
             continue
         (ik,), (iv,) = rw.consumers(k), rw.consumers(v)
+        k_src, v_src, links = k, v, ()
+        if rw.bsyms[ik].sym.name != "index_copy_inplace" and not _kv8_fusion_off():
+            qk, qv = _e4m3_quantise_chain(rw, k), _e4m3_quantise_chain(rw, v)
+            if qk is None or qv is None:
+                continue
+            k_src, v_src, links = rw.bsyms[qk[-1]].output, rw.bsyms[qv[-1]].output, (*qk, *qv)
+            if rw.uses(k_src) != 1 or rw.uses(v_src) != 1:
+                continue
+            (ik,), (iv,) = rw.consumers(k_src), rw.consumers(v_src)
         ck, cv = rw.bsyms[ik], rw.bsyms[iv]
         if ck.sym.name != "index_copy_inplace" or cv.sym.name != "index_copy_inplace":
             continue
         wk, wv = operands(ck), operands(cv)
-        if wk["dim"] != 2 or wv["dim"] != 2 or wk["src"] is not k or wv["src"] is not v:
+        if wk["dim"] != 2 or wv["dim"] != 2 or wk["src"] is not k_src or wv["src"] is not v_src:
             continue
         bk, bv, pos = wk["buf"], wv["buf"], wk["index"]
         if getattr(pos, "name", None) != getattr(wv["index"], "name", 1):
             continue
-        if pos.dtype != torch.int64 or bk.dtype != k.dtype or bv.dtype != v.dtype:
+        if pos.dtype != torch.int64 or bk.dtype != k_src.dtype or bv.dtype != v_src.dtype:
             continue
         # the fused op needs the caches and positions: emit it where the RoPE was when they exist
         # there (LitGPT), else at the later cache write (HF computes the positions after the RoPE),
@@ -966,8 +1033,59 @@ def _fuse_kv_cache_writes(trace):
             if any(lo < j < at for t in (ck.output, cv.output, bk, bv) for j in rw.consumers(t)):
                 continue
         rw.replace(at, hip_qkv_rope_cache.bind(*b.args, bk, bv, pos, output=(q, ck.output, cv.output)))
-        rw.drop(*({i, ik, iv} - {at}))
+        rw.drop(*({i, ik, iv, *links} - {at}))
     return rw.finish(f"hipex: {rw.replaced} KV-cache write pair(s) fused into RoPE")
+
+
+def _e4m3_dequantised(rw, t, dtype):
+    """``(cache, view position, to position)`` when ``t = to(view(cache, float8_e4m3fn), dtype)`` of a
+    uint8 ``cache``, else None."""
+    j = rw.producer(t)
+    if j is None or rw.touched(j):
+        return None
+    b = rw.bsyms[j]
+    if b.sym.name not in ("to", "torch_to") or _only_tensor_arg(b, 1) is None or b.args[1] is not dtype:
+        return None
+    f = b.args[0]
+    jv = rw.producer(f)
+    if f.dtype != torch.float8_e4m3fn or jv is None or rw.touched(jv):
+        return None
+    bv = rw.bsyms[jv]
+    if bv.sym.name not in ("view", "torch_view") or _only_tensor_arg(bv, 1) is None:
+        return None
+    if bv.args[1] is not torch.float8_e4m3fn or bv.args[0].dtype != torch.uint8:
+        return None
+    return bv.args[0], jv, j
+
+
+def _fuse_kv8_reads(trace):
+    """``hip_decode_attn(q, to(view(kc, float8_e4m3fn), q.dtype), to(view(vc, float8_e4m3fn), q.dtype), ...)``
+    over uint8 caches -> ``hip_decode_attn_kv8(q, kc, vc, ...)``: the decode kernel unpacks the e4m3
+    bytes itself, so a decode step neither converts nor re-reads the whole cache at 16 bits.  The
+    dequantising view / to are dropped when nothing else reads them."""
+    if _kv8_fusion_off():
+        return trace
+    rw = Rewrite(trace, ex)
+    for i, b in enumerate(rw.bsyms):
+        if b.sym is not hip_decode_attn:
+            continue
+        p = operands(b)
+        q = p["q"]
+        dk, dv = _e4m3_dequantised(rw, p["k"], q.dtype), _e4m3_dequantised(rw, p["v"], q.dtype)
+        if dk is None or dv is None:
+            continue
+        (kc, *at_k), (vc, *at_v) = dk, dv
+        # the kernel reads the caches where the attention stands: nothing may write them after the views
+        first = min(at_k[0], at_v[0])
+        if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ()) for c in (kc, vc) for j in rw.consumers(c)):
+            continue
+        rw.replace(i, hip_decode_attn_kv8.bind(q, kc, vc, p["mask"], p["causal"], p["scale"], output=b.output))
+        for (jv, jt), t in ((at_k, p["k"]), (at_v, p["v"])):
+            if rw.uses(t) == 1:
+                rw.drop(jt)
+                if rw.uses(rw.bsyms[jv].output) == 1:
+                    rw.drop(jv)
+    return rw.finish(f"hipex: {rw.replaced} decode attention(s) read their e4m3 KV cache directly")
 
 
 def _fuse_rms_bwd_residual(trace):
@@ -1357,7 +1475,7 @@ _PASSES = (
     partial(_fuse_decode, kind=_MXFP4_DECODE, folds=("gate", "act", "residual", "norm", "group"),
             message="hipex: MXFP4 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
                     "{norm} norm prologue(s), {group} group(s))"),
-    _fuse_swiglu_gemms, _fuse_kv_cache_writes,
+    _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv8_reads,
     partial(_fuse_decode, kind=_BF16_DECODE, folds=("group",), message="hipex: {group} grouped decode projection launch(es)"),
     _fuse_qkv_rope_gemm, _fuse_fp8_qkv_rope_gemm, _fuse_attn_bwd_rope,
 )
@@ -1736,6 +1854,22 @@ def _decode_attn_impl(q, k, v, mask, causal, scale):
 
 
 hip_decode_attn = ex.register_operator("hip_decode_attn", meta=_decode_attn_meta, fn=_decode_attn_impl)
+
+
+def _decode_attn_kv8_meta(q, k8, v8, mask, causal, scale):
+    return TensorProxy(like=q)
+
+
+def _decode_attn_kv8_impl(q, k8, v8, mask, causal, scale):
+    from ..ops.attention import decode_attn, decode_attn_kv8, decode_attn_kv8_supported
+
+    if decode_attn_kv8_supported(q, k8, v8):
+        return decode_attn_kv8(q, k8, v8, mask, causal, scale)
+    f8 = torch.float8_e4m3fn  # a head dim the e4m3 kernel does not take: the program as the model spells it
+    return decode_attn(q, k8.view(f8).to(q.dtype), v8.view(f8).to(q.dtype), mask, causal, scale)
+
+
+hip_decode_attn_kv8 = ex.register_operator("hip_decode_attn_kv8", meta=_decode_attn_kv8_meta, fn=_decode_attn_kv8_impl)
 
 
 def _broadcastable(shape, target) -> bool:

@@ -204,14 +204,30 @@ def _norm(config: Config, size: int) -> nn.Module:
 class KVCache(nn.Module):
     """Static key/value cache (LitGPT ``KVCache``): [B, n_query_groups, max_seq, head_size] buffers
     updated in place at ``input_pos``.  Static storage keeps the decode step's addresses fixed, so
-    a compiled decode step is a cache hit every token and can be replayed as one hipGraph."""
+    a compiled decode step is a cache hit every token and can be replayed as one hipGraph.
+
+    ``dtype=torch.float8_e4m3fn`` keeps the cache as unscaled, saturating OCP e4m3 in ``uint8``
+    buffers (the stored-fp8 convention of ``transforms/fp8_inference.py``): half the bytes per token.
+    Writes clamp to +-448 before the cast (torch's cast alone turns larger magnitudes into NaN, the
+    kernels saturate); reads dequantise exactly to the dtype of the incoming k / v."""
 
     def __init__(self, k_shape, v_shape, device=None, dtype=None):
         super().__init__()
+        if dtype == torch.float8_e4m3fn:
+            dtype = torch.uint8
+        elif dtype is not None and dtype.is_floating_point and dtype.itemsize == 1:
+            raise ValueError(f"KV cache: the only 8-bit float cache is torch.float8_e4m3fn, got {dtype}")
         self.register_buffer("k", torch.zeros(k_shape, device=device, dtype=dtype), persistent=False)
         self.register_buffer("v", torch.zeros(v_shape, device=device, dtype=dtype), persistent=False)
 
     def forward(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        if self.k.dtype == torch.uint8:
+            f8 = torch.float8_e4m3fn
+            k8 = k.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
+            v8 = v.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
+            k_all = self.k.index_copy_(2, input_pos, k8)
+            v_all = self.v.index_copy_(2, input_pos, v8)
+            return k_all.view(f8).to(k.dtype), v_all.view(f8).to(v.dtype)
         k_all = self.k.index_copy_(2, input_pos, k.to(self.k.dtype))
         v_all = self.v.index_copy_(2, input_pos, v.to(self.v.dtype))
         return k_all, v_all
@@ -390,7 +406,9 @@ class GPT(nn.Module):
 
     def set_kv_cache(self, batch_size: int, max_seq_length: Optional[int] = None, device=None,
                      dtype: Optional[torch.dtype] = None) -> None:
-        """Allocates a static KV cache in every block and the causal mask for incremental decoding."""
+        """Allocates a static KV cache in every block and the causal mask for incremental decoding.
+        ``dtype=torch.float8_e4m3fn`` stores the caches as unscaled, saturating e4m3 in ``uint8`` buffers
+        (see :class:`KVCache`); any other 8-bit float dtype raises ``ValueError``."""
         c = self.config
         max_seq_length = max_seq_length or c.block_size
         dtype = dtype or self.lm_head.weight.dtype

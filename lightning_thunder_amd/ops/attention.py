@@ -390,10 +390,21 @@ def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
     return _rows_in_place(t)
 
 
-def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = None):
-    """q [B, Hq, T, D] (T <= 16), k/v [B, Hkv, S, D], mask bool broadcastable to [B, Hq, T, S] -> [B, Hq, T, D]."""
+def decode_launch_shape(rows: int, S: int):
+    """(wsplit, nsplit, chunk) of a decode launch over ``rows`` query rows and ``S`` keys: the same
+    for every cache element type."""
+    # few rows (batch-1 decode): one row per workgroup with its 4 waves splitting the keys
+    wsplit = rows < 256
+    blocks = rows if wsplit else (rows + 3) // 4
+    # split the cache so that a decode step still launches >= ~256 workgroups (flash-decoding)
+    nsplit = max(1, min((256 + blocks - 1) // blocks, S // 256))  # a split is worth a combine launch from ~256 keys
+    chunk = ((S + nsplit - 1) // nsplit + 63) // 64 * 64
+    nsplit = (S + chunk - 1) // chunk
+    return wsplit, nsplit, chunk
+
+
+def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None):
     lib = require()
-    q, k, v = _aligned_rows(q), _aligned_rows(k), _aligned_rows(v)
     B, Hq, T, D = q.shape
     Hkv, S = k.shape[1], k.shape[2]
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -403,13 +414,7 @@ def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = 
     else:
         ms = (0, 0, 0, 0)
     rows = B * Hq * T
-    # few rows (batch-1 decode): one row per workgroup with its 4 waves splitting the keys
-    wsplit = rows < 256
-    blocks = rows if wsplit else (rows + 3) // 4
-    # split the cache so that a decode step still launches >= ~256 workgroups (flash-decoding)
-    nsplit = max(1, min((256 + blocks - 1) // blocks, S // 256))  # a split is worth a combine launch from ~256 keys
-    chunk = ((S + nsplit - 1) // nsplit + 63) // 64 * 64
-    nsplit = (S + chunk - 1) // chunk
+    wsplit, nsplit, chunk = decode_launch_shape(rows, S)
     o = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
     ws_acc = ws_ml = None
     if nsplit > 1:
@@ -418,8 +423,45 @@ def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = 
     st = (ctypes.c_int64 * 13)(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
                                v.stride(0), v.stride(1), v.stride(2), *ms)
     mptr = None if mask is None else mask.data_ptr()
-    rc = lib.lta_decode_attn(dcode(q), ptr(q), ptr(k), ptr(v), mptr, ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq, Hkv, T, S, D,
+    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), mptr, ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq, Hkv, T, S, D,
                              ctypes.cast(st, ctypes.c_void_p), chunk, nsplit, int(causal), float(sc), int(wsplit),
                              stream_ptr(q.device))
-    check(rc, "lta_decode_attn")
+    check(rc, entry)
     return o
+
+
+def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = None):
+    """q [B, Hq, T, D] (T <= 16), k/v [B, Hkv, S, D], mask bool broadcastable to [B, Hq, T, S] -> [B, Hq, T, D]."""
+    q, k, v = _aligned_rows(q), _aligned_rows(k), _aligned_rows(v)
+    return _decode_launch("lta_decode_attn", q, k, v, mask, causal, scale)
+
+
+register_signature("lta_decode_attn_kv8", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                           c_float, c_int, c_void_p])
+
+
+def decode_attn_kv8_supported(q, k8, v8) -> bool:
+    """What the e4m3-cache decode kernel takes: 16-bit q of head dim 64 / 128, uint8 k / v."""
+    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
+            and q.shape[2] <= DECODE_MAX_QUERIES and k8.dtype == torch.uint8 and v8.dtype == torch.uint8
+            and k8.dim() == 4 and k8.shape == v8.shape and k8.shape[-1] == q.shape[-1] and k8.shape[0] == q.shape[0]
+            and k8.shape[1] > 0 and q.shape[1] % k8.shape[1] == 0)
+
+
+def _rows8_in_place(t):
+    """A uint8 cache as the kernel reads it (head dim contiguous, 16-byte aligned rows, strides a
+    multiple of 16 bytes) in place, else a dense copy in fresh memory."""
+    if t.stride(-1) == 1 and all(s % 16 == 0 for s in t.stride()[:-1]) and t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format) if t.is_contiguous() else t.contiguous()
+
+
+def decode_attn_kv8(q, k8, v8, mask=None, causal: bool = False, scale: float | None = None):
+    """``decode_attn`` over an unscaled OCP e4m3 cache: k8 / v8 uint8 [B, Hkv, S, D] (the bytes of
+    ``float8_e4m3fn``), unpacked in the kernel; q and the result are bf16 / fp16."""
+    if not decode_attn_kv8_supported(q, k8, v8):
+        raise ValueError(f"decode_attn_kv8: unsupported operands q {q.dtype} {tuple(q.shape)}, "
+                         f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}")
+    q, k8, v8 = _aligned_rows(q), _rows8_in_place(k8), _rows8_in_place(v8)
+    return _decode_launch("lta_decode_attn_kv8", q, k8, v8, mask, causal, scale)

@@ -23,17 +23,50 @@ namespace {
 
 constexpr int kRowsPerBlock = 4;
 
+// One 16-byte load of an e4m3 cache row (uint8 storage) as 16 fp32 values, unpacked two at a time by the
+// hardware conversion (OCP e4m3 on gfx950; exact).
+__device__ __forceinline__ void load16_e4m3(const uint8_t* p, float (&f)[16]) {
+  const uint4 x = *reinterpret_cast<const uint4*>(p);
+  const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    f[4 * i + 0] = lo[0];
+    f[4 * i + 1] = lo[1];
+    f[4 * i + 2] = hi[0];
+    f[4 * i + 3] = hi[1];
+  }
+}
+
 // WSPLIT (few rows, e.g. batch-1 decode: 32 rows would occupy 8 CUs): one row per block, the 4
 // waves take interleaved 64-key blocks of the row's range and merge their (m, l, acc) through LDS,
 // so a row's serial key loop is 4x shorter without a second launch.
-template <typename T, int D, bool WSPLIT>
+// KV is the cache's element type: T itself, or uint8_t for an unscaled e4m3 cache (same structure and
+// the same fp32 arithmetic in the same order; only the row loads differ).  The e4m3 kernels start their
+// sums from -0, the additive identity that keeps a stored -0 (byte 0x80) a -0 when it is all a row
+// attends to; the 16-bit kernels keep their +0 start, and every other result is the same either way.
+template <typename KV>
+constexpr float kSumStart = sizeof(KV) == 1 ? -0.f : 0.f;
+
+// acc / l rounded to T.  For the e4m3 kernels the product first settles in a register: hipcc otherwise folds
+// the multiply and the fp16 conversion into one v_fma_mixlo_f16 (x * y + 0), and the + 0 turns a -0 into +0.
+template <typename T, typename KV>
+__device__ __forceinline__ T normalised(float acc, float inv) {
+  float r = acc * inv;
+  if constexpr (sizeof(KV) == 1) asm volatile("" : "+v"(r));
+  return from_f32<T>(r);
+}
+
+template <typename T, typename KV, int D, bool WSPLIT>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
-    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const uint8_t* __restrict__ mask,
+    const T* __restrict__ q, const KV* __restrict__ k, const KV* __restrict__ v, const uint8_t* __restrict__ mask,
     T* __restrict__ o, float* __restrict__ ws_acc, float* __restrict__ ws_ml, int B, int Hq, int Hkv, int Tq, int S,
     int64_t qsb, int64_t qsh, int64_t qst, int64_t ksb, int64_t ksh, int64_t kss, int64_t vsb, int64_t vsh,
     int64_t vss, int64_t msb, int64_t msh, int64_t mst, int64_t mss, int chunk, int causal, float scale) {
   constexpr int DPL = D / 64;          // output dims per lane after the final reduce-scatter
-  constexpr int NV = Vec16<T>::N;      // elements per 16-byte load
+  constexpr bool kE4M3 = sizeof(KV) == 1;
+  constexpr int NV = 16 / sizeof(KV);  // elements per 16-byte load
   __shared__ float q_lds[kRowsPerBlock][D];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int rows = B * Tq * Hq;
@@ -52,8 +85,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   const T* qrow = q + b * qsb + hq * qsh + t * qst;
   for (int d = lane; d < D; d += 64) q_lds[w][d] = to_f32(qrow[d]) * scale;
   __builtin_amdgcn_wave_barrier();
-  const T* kbase = k + b * ksb + hk * ksh;
-  const T* vbase = v + b * vsb + hk * vsh;
+  const KV* kbase = k + b * ksb + hk * ksh;
+  const KV* vbase = v + b * vsb + hk * vsh;
   const uint8_t* mrow = mask ? mask + b * msb + hq * msh + t * mst : nullptr;
 
   // every lane owns one key per 64-key block: QK and PV are both lane-parallel; the per-lane
@@ -61,7 +94,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   float m = -INFINITY, l = 0.f;
   float acc[D];
 #pragma unroll
-  for (int i = 0; i < D; ++i) acc[i] = 0.f;
+  for (int i = 0; i < D; ++i) acc[i] = kSumStart<KV>;
 
   for (int j0 = j_begin + (WSPLIT ? w * 64 : 0); j0 < j_end; j0 += (WSPLIT ? kRowsPerBlock * 64 : 64)) {
     const int j = j0 + lane;
@@ -70,13 +103,20 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     if (!__any(valid)) continue;  // fully masked block: no K/V traffic
     float s = -INFINITY;
     if (valid) {
-      const T* krow = kbase + (int64_t)j * kss;
+      const KV* krow = kbase + (int64_t)j * kss;
       float dot = 0.f;
 #pragma unroll
       for (int d = 0; d < D; d += NV) {
-        Vec16<T> x = load16(krow + d);
+        if constexpr (kE4M3) {
+          float x[NV];
+          load16_e4m3(krow + d, x);
 #pragma unroll
-        for (int e = 0; e < NV; ++e) dot = fmaf(q_lds[w][d + e], to_f32(x.v[e]), dot);
+          for (int e = 0; e < NV; ++e) dot = fmaf(q_lds[w][d + e], x[e], dot);
+        } else {
+          Vec16<T> x = load16(krow + d);
+#pragma unroll
+          for (int e = 0; e < NV; ++e) dot = fmaf(q_lds[w][d + e], to_f32(x.v[e]), dot);
+        }
       }
       s = dot;
     }
@@ -86,12 +126,19 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     l = l * corr + wave_sum(p);
     m = m_new;
     if (valid) {
-      const T* vrow = vbase + (int64_t)j * vss;
+      const KV* vrow = vbase + (int64_t)j * vss;
 #pragma unroll
       for (int d = 0; d < D; d += NV) {
-        Vec16<T> x = load16(vrow + d);
+        if constexpr (kE4M3) {
+          float x[NV];
+          load16_e4m3(vrow + d, x);
 #pragma unroll
-        for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(p, to_f32(x.v[e]), acc[d + e] * corr);
+          for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(p, x[e], acc[d + e] * corr);
+        } else {
+          Vec16<T> x = load16(vrow + d);
+#pragma unroll
+          for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(p, to_f32(x.v[e]), acc[d + e] * corr);
+        }
       }
     } else {
 #pragma unroll
@@ -128,7 +175,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     for (int u = 0; u < kRowsPerBlock; ++u) M = fmaxf(M, c_ml[u][0]);
     float L = 0.f;
 #pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
+    for (int i = 0; i < DPL; ++i) acc[i] = kSumStart<KV>;
 #pragma unroll
     for (int u = 0; u < kRowsPerBlock; ++u) {
       const float c = c_ml[u][0] == -INFINITY ? 0.f : __expf(c_ml[u][0] - M);
@@ -144,7 +191,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     const float inv = 1.f / l;  // fully masked row -> 0 * inf = nan, like PyTorch SDPA
     T* orow = o + (((int64_t)b * Hq + hq) * Tq + t) * D + lane * DPL;  // o is [B, Hq, Tq, D]
 #pragma unroll
-    for (int i = 0; i < DPL; ++i) orow[i] = from_f32<T>(acc[i] * inv);
+    for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV>(acc[i], inv);
   } else {
     float* wa = ws_acc + ((int64_t)split * rows + row) * D + lane * DPL;
 #pragma unroll
@@ -156,7 +203,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   }
 }
 
-template <typename T, int D>
+template <typename T, typename KV, int D>
 __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __restrict__ ws_acc,
                                                                  const float* __restrict__ ws_ml, T* __restrict__ o,
                                                                  int rows, int nsplit, int Hq, int Tq) {
@@ -167,7 +214,7 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   for (int s = 0; s < nsplit; ++s) M = fmaxf(M, ws_ml[((int64_t)s * rows + row) * 2]);
   float L = 0.f, acc[DPL];
 #pragma unroll
-  for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
+  for (int i = 0; i < DPL; ++i) acc[i] = kSumStart<KV>;
   for (int s = 0; s < nsplit; ++s) {
     const float ms = ws_ml[((int64_t)s * rows + row) * 2];
     if (ms == -INFINITY) continue;
@@ -180,28 +227,28 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   const float inv = 1.f / L;
   T* orow = o + (((int64_t)b * Hq + hq) * Tq + t) * D + lane * DPL;
 #pragma unroll
-  for (int i = 0; i < DPL; ++i) orow[i] = from_f32<T>(acc[i] * inv);
+  for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV>(acc[i], inv);
 }
 
-template <typename T, int D>
+template <typename T, typename KV, int D>
 int launch(const void* q, const void* k, const void* v, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
            int Hq, int Hkv, int Tq, int S, const int64_t* st, int chunk, int nsplit, int causal, float scale,
            int wsplit, hipStream_t stream) {
   const int rows = B * Tq * Hq;
   if (wsplit) {
-    hipLaunchKernelGGL((decode_attn_kernel<T, D, true>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
-                       (const T*)k, (const T*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
+                       (const KV*)k, (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
                        Tq, S, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11],
                        st[12], chunk, causal, scale);
   } else {
     dim3 grid((rows + kRowsPerBlock - 1) / kRowsPerBlock, nsplit);
-    hipLaunchKernelGGL((decode_attn_kernel<T, D, false>), grid, dim3(256), 0, stream, (const T*)q, (const T*)k,
-                       (const T*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
+                       (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
                        st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12],
                        chunk, causal, scale);
   }
   if (nsplit > 1)
-    hipLaunchKernelGGL((decode_attn_combine_kernel<T, D>), dim3(rows), dim3(64), 0, stream, (const float*)ws_acc,
+    hipLaunchKernelGGL((decode_attn_combine_kernel<T, KV, D>), dim3(rows), dim3(64), 0, stream, (const float*)ws_acc,
                        (const float*)ws_ml, (T*)o, rows, nsplit, Hq, Tq);
   return (int)hipGetLastError();
 }
@@ -218,11 +265,33 @@ LTA_EXPORT int lta_decode_attn(int dtype, const void* q, const void* k, const vo
   hipStream_t s = (hipStream_t)stream;
   if (Hkv <= 0 || Hq % Hkv != 0 || chunk <= 0 || nsplit <= 0) return (int)hipErrorInvalidValue;
   if (dtype == kBF16) {
-    if (D == 64) return launch<__hip_bfloat16, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-    if (D == 128) return launch<__hip_bfloat16, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+    if (D == 64) return launch<__hip_bfloat16, __hip_bfloat16, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+    if (D == 128) return launch<__hip_bfloat16, __hip_bfloat16, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
   } else if (dtype == kF16) {
-    if (D == 64) return launch<__half, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-    if (D == 128) return launch<__half, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+    if (D == 64) return launch<__half, __half, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+    if (D == 128) return launch<__half, __half, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+  }
+  return (int)hipErrorInvalidValue;
+}
+
+// The same launch over an unscaled OCP e4m3 cache: k / v are uint8 [B, Hkv, S, D] (strides in elements
+// = bytes, multiples of 16, rows 16-byte aligned); `dtype` is q's and the output's.
+LTA_EXPORT int lta_decode_attn_kv8(int dtype, const void* q, const void* k, const void* v, const void* mask, void* o,
+                                   void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                   const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit,
+                                   void* stream) {
+  using namespace lta;
+  hipStream_t s = (hipStream_t)stream;
+  if (Hkv <= 0 || Hq % Hkv != 0 || chunk <= 0 || nsplit <= 0) return (int)hipErrorInvalidValue;
+  for (int i = 3; i < 9; ++i)
+    if (strides[i] % 16) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)k | (uintptr_t)v) % 16) return (int)hipErrorInvalidValue;
+  if (dtype == kBF16) {
+    if (D == 64) return launch<__hip_bfloat16, uint8_t, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+    if (D == 128) return launch<__hip_bfloat16, uint8_t, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+  } else if (dtype == kF16) {
+    if (D == 64) return launch<__half, uint8_t, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+    if (D == 128) return launch<__half, uint8_t, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
   }
   return (int)hipErrorInvalidValue;
 }

@@ -10,6 +10,7 @@
 // Each work item moves one 16-byte chunk (8 elements) of a head row and, for rotated chunks,
 // also its partner chunk half a rope width away, so every HBM access is a 16-B vector.
 #include "common.h"
+#include "fp8_cvt.h"
 
 using namespace lta;
 
@@ -148,15 +149,27 @@ __device__ __forceinline__ void load_cs8(const C* p, float (&o)[8]) {
   }
 }
 
-template <typename T, typename C, bool BWD>
+// 8 values already rounded to T -> 8 bytes of saturating e4m3 (round to nearest even), one 8-byte store
+template <typename T>
+__device__ __forceinline__ void store8_e4m3(uint8_t* p, const Vec16<T>& x) {
+  uint2 w;
+  w.x = cvt4<false>(to_f32(x.v[0]), to_f32(x.v[1]), to_f32(x.v[2]), to_f32(x.v[3]));
+  w.y = cvt4<false>(to_f32(x.v[4]), to_f32(x.v[5]), to_f32(x.v[6]), to_f32(x.v[7]));
+  *reinterpret_cast<uint2*>(p) = w;
+}
+
+// KT: the element type of the forward's k / v destination, T or uint8_t (an unscaled e4m3 cache: the
+// row rounded to T as for a T cache, then converted, so the launch equals RoPE + clamp + cast + copy)
+template <typename T, typename C, bool BWD, typename KT = T>
 __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__ in0, const T* __restrict__ in1,
                                                            const T* __restrict__ in2, const C* __restrict__ cos_,
                                                            const C* __restrict__ sin_, T* __restrict__ out0,
-                                                           T* __restrict__ out1, T* __restrict__ out2,
+                                                           KT* __restrict__ out1, KT* __restrict__ out2,
                                                            const int64_t* __restrict__ pos, KVDst st, int Tn, int nh,
                                                            int ng, int hs, int pair_shift) {
   // fwd: in0 = qkv, out0/1/2 = q/k/v (k/v through st); bwd: in0/1/2 = dq/dk/dv, out0 = dqkv
   constexpr int VW = 8;
+  constexpr bool kE4M3 = !BWD && sizeof(KT) == 1;
   const int row = blockIdx.x;  // b * Tn + t
   const int t = row % Tn, b = row / Tn;
   const int heads = nh + 2 * ng, half = hs / 2;
@@ -167,14 +180,21 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
     const int h = it >> pair_shift, d0 = (it & ((1 << pair_shift) - 1)) * VW;
     const T* src;
     T* dst;
+    [[maybe_unused]] uint8_t* kv8 = nullptr;  // e4m3 cache: the row of a k / v head (dst unused for it)
     if constexpr (!BWD) {
       src = in0 + ((int64_t)row * heads + h) * hs;
       if (h < nh) {
         dst = out0 + (((int64_t)b * nh + h) * Tn + t) * hs;
       } else {
         const int64_t s = pos ? pos[t] : t;
-        dst = h < nh + ng ? out1 + b * st.ksb + (h - nh) * st.ksg + s * st.kss
-                          : out2 + b * st.vsb + (h - nh - ng) * st.vsg + s * st.vss;
+        if constexpr (kE4M3) {
+          dst = nullptr;
+          kv8 = h < nh + ng ? out1 + b * st.ksb + (h - nh) * st.ksg + s * st.kss
+                            : out2 + b * st.vsb + (h - nh - ng) * st.vsg + s * st.vss;
+        } else {
+          dst = h < nh + ng ? out1 + b * st.ksb + (h - nh) * st.ksg + s * st.kss
+                            : out2 + b * st.vsb + (h - nh - ng) * st.vsg + s * st.vss;
+        }
       }
     } else {
       dst = out0 + ((int64_t)row * heads + h) * hs;
@@ -184,8 +204,13 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
     }
     const Vec16<T> x1 = load16(src + d0), x2 = load16(src + d0 + half);
     if (h >= nh + ng) {  // v: layout change only
-      store16(dst + d0, x1);
-      store16(dst + d0 + half, x2);
+      if constexpr (kE4M3) {
+        store8_e4m3(kv8 + d0, x1);
+        store8_e4m3(kv8 + d0 + half, x2);
+      } else {
+        store16(dst + d0, x1);
+        store16(dst + d0 + half, x2);
+      }
       continue;
     }
     float c1[8], s1[8], c2[8], s2[8];
@@ -203,6 +228,13 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
       } else {  // transpose of the rotation
         o1.v[j] = from_f32<T>(a * c1[j] + bb * s2[j]);
         o2.v[j] = from_f32<T>(bb * c2[j] - a * s1[j]);
+      }
+    }
+    if constexpr (kE4M3) {
+      if (kv8 != nullptr) {
+        store8_e4m3(kv8 + d0, o1);
+        store8_e4m3(kv8 + d0 + half, o2);
+        continue;
       }
     }
     store16(dst + d0, o1);
@@ -282,6 +314,32 @@ LTA_EXPORT int lta_qkv_rope_cache_fwd(int dtype, int cdtype, const void* qkv, co
   const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
   return qkv_rope_fwd_launch(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, (const int64_t*)pos, st, B, Tn, nh, ng, hs,
                              rope_n, stream);
+}
+
+// As lta_qkv_rope_cache_fwd with uint8 caches holding unscaled OCP e4m3: k (rotated) and v are rounded
+// to the activation dtype, saturated to +-448 and converted (round to nearest even), 8 bytes per store.
+// Row-kernel shapes only (rope_n == hs, hs / 16 a power of two, 16-bit activations): -2 otherwise.
+LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
+                                          void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
+                                          int Tn, int nh, int ng, int hs, int rope_n, hipStream_t stream) {
+  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
+  if (((uintptr_t)kc | (uintptr_t)vc) % 8) return -2;
+  const int sh = row_pair_shift(dtype, hs, rope_n);
+  if (sh < 0 || dtype == kF32) return -2;
+  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  auto launch = [&](auto t, auto c) {
+    using T = decltype(t);
+    using C = decltype(c);
+    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t>), dim3(B * Tn), dim3(256), 0, stream, (const T*)qkv,
+                       (const T*)nullptr, (const T*)nullptr, (const C*)cos_, (const C*)sin_, (T*)q, (uint8_t*)kc,
+                       (uint8_t*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs, sh);
+    return (int)hipGetLastError();
+  };
+  if (dtype == kBF16 && cdtype == kF32) return launch(__hip_bfloat16{}, float{});
+  if (dtype == kBF16 && cdtype == kBF16) return launch(__hip_bfloat16{}, __hip_bfloat16{});
+  if (dtype == kF16 && cdtype == kF32) return launch(__half{}, float{});
+  if (dtype == kF16 && cdtype == kF16) return launch(__half{}, __half{});
+  return -1;
 }
 
 LTA_EXPORT int lta_qkv_rope_bwd(int dtype, int cdtype, const void* dq, const void* dk, const void* dv, const void* cos_,

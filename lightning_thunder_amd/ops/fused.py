@@ -11,6 +11,9 @@ register_signature("lta_qkv_rope_fwd", [c_int, c_int, c_void_p, c_void_p, c_void
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
 register_signature("lta_qkv_rope_cache_fwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
+register_signature("lta_qkv_rope_cache_fwd_kv8", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                  c_void_p])
 register_signature("lta_qkv_rope_bwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
 register_signature("lta_swiglu_fwd", [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -48,9 +51,27 @@ def qkv_rope_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int
     return q, k, v
 
 
-def qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups: int, head_size: int) -> bool:
-    """Static caches [B, ng, S, hs] (head dim contiguous, 16-byte aligned rows) and int64 positions."""
+def _row_kernel_shape(dtype, head_size: int, rope_n: int) -> bool:
+    """What csrc/rope.hip's one-row-per-workgroup kernel takes (its ``row_pair_shift >= 0``)."""
+    pairs = head_size // 16
+    return (dtype in (torch.bfloat16, torch.float16) and rope_n == head_size and head_size % 16 == 0
+            and pairs > 0 and pairs & (pairs - 1) == 0)
+
+
+def qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups: int, head_size: int, rope_n: int | None = None) -> bool:
+    """Static caches [B, ng, S, hs] (head dim contiguous, 16-byte aligned rows) and int64 positions.
+    uint8 caches (unscaled e4m3, 8-byte aligned rows) only at the row kernel's shapes: full rotation
+    (``rope_n``, taken as ``head_size`` when not given) and ``head_size / 16`` a power of two."""
     B, T, _ = qkv.shape
+    if kc.dtype == torch.uint8 and vc.dtype == torch.uint8:
+        if not _row_kernel_shape(qkv.dtype, head_size, head_size if rope_n is None else rope_n):
+            return False
+        for c in (kc, vc):
+            if c.dim() != 4 or tuple(c.shape[:2]) != (B, n_query_groups) or c.shape[3] != head_size:
+                return False
+            if c.stride(3) != 1 or any(st % 8 for st in c.stride()[:3]) or c.data_ptr() % 8:
+                return False
+        return pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == T and pos.is_contiguous()
     for c in (kc, vc):
         if c.dtype != qkv.dtype or c.dim() != 4 or tuple(c.shape[:2]) != (B, n_query_groups) or c.shape[3] != head_size:
             return False
@@ -61,7 +82,9 @@ def qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups: int, head_size: i
 
 def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kc, vc, pos):
     """qkv split + RoPE with k / v written in place into the static caches ``kc`` / ``vc`` at rows
-    ``pos`` (the decode step's ``index_copy_`` fused into the same launch).  Returns (q, kc, vc)."""
+    ``pos`` (the decode step's ``index_copy_`` fused into the same launch).  Returns (q, kc, vc).
+    uint8 caches receive the rows as unscaled saturating e4m3: bit for bit
+    ``k.clamp(-448, 448).to(float8_e4m3fn).view(uint8)`` of ``qkv_rope_fwd``'s k (and v)."""
     lib = require()
     qkv = _c(qkv)
     B, T, _ = qkv.shape
@@ -73,10 +96,10 @@ def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_siz
         cos, sin = cos.float(), sin.float()
     q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
     st = (ctypes.c_int64 * 6)(*kc.stride()[:3], *vc.stride()[:3])
-    rc = lib.lta_qkv_rope_cache_fwd(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), ptr(kc), ptr(vc),
-                                    ptr(pos), st, B, T, n_head, n_query_groups, head_size, rope_n,
-                                    stream_ptr(qkv.device))
-    check(rc, "lta_qkv_rope_cache_fwd")
+    entry = "lta_qkv_rope_cache_fwd_kv8" if kc.dtype == torch.uint8 else "lta_qkv_rope_cache_fwd"
+    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), ptr(kc), ptr(vc),
+                             ptr(pos), st, B, T, n_head, n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
+    check(rc, entry)
     return q, kc, vc
 
 
