@@ -31,8 +31,10 @@ def _percentile(xs, q):
     return s[min(len(s) - 1, int(round(q * (len(s) - 1))))]
 
 
-# --kv-cache-dtype: "model" keeps the cache in the model's dtype, "fp8" stores unscaled e4m3 (half the bytes)
-KV_CACHE_DTYPES = {"model": torch.bfloat16, "fp8": torch.float8_e4m3fn}
+# --kv-cache-dtype: "model" keeps the cache in the model's dtype, "fp8" stores unscaled e4m3 (half the bytes),
+# "fp8-row" e4m3 with one power-of-two scale byte per (token, kv head) row (set_kv_cache(..., scale="row"))
+KV_CACHE_DTYPES = {"model": torch.bfloat16, "fp8": torch.float8_e4m3fn, "fp8-row": torch.float8_e4m3fn}
+KV_CACHE_SCALES = {"model": None, "fp8": None, "fp8-row": "row"}
 
 
 def _build(args, device):
@@ -48,7 +50,7 @@ def _build(args, device):
     model.requires_grad_(False)
     model.eval()
     model.set_kv_cache(args.batch_size, args.input_length + args.output_length + 8, device=device,
-                       dtype=KV_CACHE_DTYPES[args.kv_cache_dtype])
+                       dtype=KV_CACHE_DTYPES[args.kv_cache_dtype], scale=KV_CACHE_SCALES[args.kv_cache_dtype])
     return model, cfg
 
 
@@ -125,7 +127,7 @@ def run(mode: str, args) -> dict:
         "batch_size": B, "input_length": args.input_length, "output_length": n_out,
         "dtype": "bf16", "kv_cache_dtype": args.kv_cache_dtype,
         "kv_cache_gib": round(sum(c.numel() * c.element_size() for b in model.transformer.h
-                                  for c in (b.attn.kv_cache.k, b.attn.kv_cache.v)) / 2 ** 30, 3),
+                                  for c in b.attn.kv_cache.buffers()) / 2 ** 30, 3),  # scale buffers included
         "memory_allocated_gib": round(torch.cuda.memory_allocated(device) / 2 ** 30, 3),  # held after the last step
         "max_memory_allocated_gib": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 3),
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
@@ -143,7 +145,8 @@ def main(argv=None):
     p.add_argument("--modes", default="eager,thunder,hipgraph")
     p.add_argument("--n-layer", type=int, default=None, help="debug only")
     p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_DTYPES), default="model",
-                   help="'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes)")
+                   help="'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes), 'fp8-row' as e4m3 "
+                        "with one power-of-two scale byte per (token, kv head) row")
     args = p.parse_args(argv)
     if args.output_length < 1:
         p.error("--output-length must be >= 1")

@@ -940,6 +940,36 @@ hip_qkv_rope_cache.written_args = (7, 8)  # kc, vc; qkv/cos/sin/pos are only rea
 _E4M3_MAX = 448.0
 
 
+# the scaled e4m3 cache (ops/kv8.py): bytes and one scale byte per (token, kv head) row, all four written
+def _qkv_rope_cache_s8_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, k_scale, v_scale, pos):
+    B, T, _ = qkv.shape
+    return (TensorProxy(like=qkv, shape=(B, n_head, T, head_size)), TensorProxy(like=kc), TensorProxy(like=vc),
+            TensorProxy(like=k_scale), TensorProxy(like=v_scale))
+
+
+def _qkv_rope_cache_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, k_scale, v_scale, pos):
+    from ..ops.fused import qkv_rope_cache_fwd, qkv_rope_cache_scaled_supported, qkv_rope_fwd
+    from ..ops.kv8 import quantise_rows
+
+    if qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_groups, head_size, rope_n):
+        return qkv_rope_cache_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos,
+                                  k_scale=k_scale, v_scale=v_scale)
+    # a shape the row kernel does not take: the program as the model spells it
+    q, k, v = qkv_rope_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
+    pos = pos if pos.dtype == torch.int64 else pos.long()
+    (k8, ks), (v8, vs) = quantise_rows(k), quantise_rows(v)
+    return (q, kc.index_copy_(2, pos, k8), vc.index_copy_(2, pos, v8), k_scale.index_copy_(2, pos, ks),
+            v_scale.index_copy_(2, pos, vs))
+
+
+hip_qkv_rope_cache_s8 = ex.register_operator("hip_qkv_rope_cache_s8", meta=_qkv_rope_cache_s8_meta,
+                                             fn=_qkv_rope_cache_s8_impl, tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
+hip_qkv_rope_cache_s8.written_args = (7, 8, 9, 10)  # kc, vc, k_scale, v_scale
+_KV8_QUANTISE_IDS = ("custom_op.lta::kv8_quantise_rows", "custom_op.custom_op_impl_custom_op_lta_kv8_quantise_rows")
+_KV8_DEQUANTISE_IDS = ("custom_op.lta::kv8_dequantise_rows",
+                       "custom_op.custom_op_impl_custom_op_lta_kv8_dequantise_rows")
+
+
 def _kv8_fusion_off() -> bool:
     """LTA_KV8_FUSION=0 keeps the e4m3 KV cache's quantising writes and dequantising reads as the
     separate operations the model spells (A/B against the two fused kernels)."""
@@ -981,6 +1011,60 @@ def _e4m3_quantise_chain(rw, t):
     return chain
 
 
+def _fuse_scaled_kv_cache_write(rw, i, ik, iv) -> None:
+    """The scaled e4m3 cache's write behind the ``hip_qkv_rope`` at ``i``: ``k8, ks = kv8_quantise_rows(k)``
+    at ``ik`` and the same for v at ``iv``, each of the four results read once, by an
+    ``index_copy_inplace`` along dim 2 at one ``pos`` into a uint8 buffer -> one ``hip_qkv_rope_cache_s8``.
+    Anything else (a result read twice, another position, v through the unscaled chain) stays."""
+    b = rw.bsyms[i]
+    q, k, v = b.output
+    srcs, copies = [], []
+    for j, t in ((ik, k), (iv, v)):
+        bq = rw.bsyms[j]
+        if rw.touched(j) or bq.sym.id not in _KV8_QUANTISE_IDS or _only_tensor_arg(bq) is not t:
+            return
+        outs = bq.output
+        if not isinstance(outs, (tuple, list)) or len(outs) != 2 or not all(isinstance(o, TensorProxy) for o in outs):
+            return
+        srcs.append(outs)
+    (k8, ks), (v8, vs) = srcs
+    pos = None
+    for t in (k8, v8, ks, vs):  # the operator's order: byte caches, then scale caches
+        if rw.uses(t) != 1:
+            return
+        (j,) = rw.consumers(t)
+        c = rw.bsyms[j]
+        if rw.touched(j) or c.sym.name != "index_copy_inplace":
+            return
+        w = operands(c)
+        if w["dim"] != 2 or w["src"] is not t or not isinstance(w["buf"], TensorProxy) or w["buf"].dtype != torch.uint8:
+            return
+        if pos is None:
+            pos = w["index"]
+            if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64:
+                return
+        elif getattr(w["index"], "name", None) != pos.name:
+            return
+        copies.append((j, c, w["buf"]))
+    if len({j for j, _, _ in copies}) != 4:
+        return
+    bufs = [buf for _, _, buf in copies]
+    # placement as for the unscaled write: where the RoPE was when caches and positions exist there, else
+    # at the last cache write, provided nothing in between reads q, a written cache or an earlier write's result
+    ready = max(rw.producer(t, -1) for t in (*bufs, pos))
+    at = i
+    if ready >= i:
+        at = max(j for j, _, _ in copies)
+        if any(i < j < at for j in rw.consumers(q)) or ready >= at:
+            return
+        lo = min(j for j, _, _ in copies)
+        if any(lo < j < at and j not in {x for x, _, _ in copies}
+               for t in (*(c.output for _, c, _ in copies), *bufs) for j in rw.consumers(t)):
+            return
+    rw.replace(at, hip_qkv_rope_cache_s8.bind(*b.args, *bufs, pos, output=(q, *(c.output for _, c, _ in copies))))
+    rw.drop(*({i, ik, iv, *(j for j, _, _ in copies)} - {at}))
+
+
 def _fuse_kv_cache_writes(trace):
     """``q, k, v = hip_qkv_rope(...); kc = index_copy_inplace(cache_k, 2, pos, k);
     vc = index_copy_inplace(cache_v, 2, pos, v)`` (k, v used nowhere else) ->
@@ -989,7 +1073,11 @@ def _fuse_kv_cache_writes(trace):
 
     With uint8 (unscaled e4m3) caches k and v reach their write through
     ``clamp(-448, 448) -> to(float8_e4m3fn) -> view(uint8)``, every link read once; the kernel
-    converts in the same launch (eight launches fewer per layer)."""
+    converts in the same launch (eight launches fewer per layer).
+
+    With the scaled e4m3 cache k and v each pass through ``kv8_quantise_rows`` and their bytes and scale
+    bytes through four ``index_copy_inplace`` at one ``pos``: ``hip_qkv_rope_cache_s8``
+    (``_fuse_scaled_kv_cache_write``)."""
     rw = Rewrite(trace, ex)
     for i, b in enumerate(rw.bsyms):
         if b.sym is not hip_qkv_rope:
@@ -998,6 +1086,10 @@ def _fuse_kv_cache_writes(trace):
         if rw.uses(k) != 1 or rw.uses(v) != 1:
             continue
         (ik,), (iv,) = rw.consumers(k), rw.consumers(v)
+        if rw.bsyms[ik].sym.id in _KV8_QUANTISE_IDS or rw.bsyms[iv].sym.id in _KV8_QUANTISE_IDS:
+            if not _kv8_fusion_off():
+                _fuse_scaled_kv_cache_write(rw, i, ik, iv)
+            continue
         k_src, v_src, links = k, v, ()
         if rw.bsyms[ik].sym.name != "index_copy_inplace" and not _kv8_fusion_off():
             qk, qv = _e4m3_quantise_chain(rw, k), _e4m3_quantise_chain(rw, v)
@@ -1058,11 +1150,32 @@ def _e4m3_dequantised(rw, t, dtype):
     return bv.args[0], jv, j
 
 
+def _kv8_rows_dequantised(rw, t, dtype):
+    """``(cache, scale cache, position)`` when ``t = kv8_dequantise_rows(cache, scales, dtype)`` of uint8
+    operands, else None."""
+    j = rw.producer(t)
+    if j is None or rw.touched(j):
+        return None
+    b = rw.bsyms[j]
+    if b.sym.id not in _KV8_DEQUANTISE_IDS:
+        return None
+    p = operands(b, ("b", "scales", "dtype"))
+    c, s = p["b"], p["scales"]
+    if p["dtype"] is not dtype or not all(isinstance(x, TensorProxy) and x.dtype == torch.uint8 for x in (c, s)):
+        return None
+    return c, s, j
+
+
 def _fuse_kv8_reads(trace):
     """``hip_decode_attn(q, to(view(kc, float8_e4m3fn), q.dtype), to(view(vc, float8_e4m3fn), q.dtype), ...)``
     over uint8 caches -> ``hip_decode_attn_kv8(q, kc, vc, ...)``: the decode kernel unpacks the e4m3
     bytes itself, so a decode step neither converts nor re-reads the whole cache at 16 bits.  The
-    dequantising view / to are dropped when nothing else reads them."""
+    dequantising view / to are dropped when nothing else reads them.
+
+    The scaled cache the same way: ``hip_decode_attn(q, kv8_dequantise_rows(kc, ks, q.dtype),
+    kv8_dequantise_rows(vc, vs, q.dtype), ...)`` -> ``hip_decode_attn_kv8s(q, kc, vc, ks, vs, ...)``.  k and v
+    must be of one kind, and nothing may write a byte or scale cache in place between its dequantise and
+    the attention."""
     if _kv8_fusion_off():
         return trace
     rw = Rewrite(trace, ex)
@@ -1071,6 +1184,19 @@ def _fuse_kv8_reads(trace):
             continue
         p = operands(b)
         q = p["q"]
+        sk, sv = _kv8_rows_dequantised(rw, p["k"], q.dtype), _kv8_rows_dequantised(rw, p["v"], q.dtype)
+        if sk is not None and sv is not None:
+            (kc, ks, jk), (vc, vs, jv) = sk, sv
+            first = min(jk, jv)
+            if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
+                   for c in (kc, vc, ks, vs) for j in rw.consumers(c)):
+                continue
+            rw.replace(i, hip_decode_attn_kv8s.bind(q, kc, vc, ks, vs, p["mask"], p["causal"], p["scale"],
+                                                    output=b.output))
+            for j, t in ((jk, p["k"]), (jv, p["v"])):
+                if rw.uses(t) == 1:
+                    rw.drop(j)
+            continue
         dk, dv = _e4m3_dequantised(rw, p["k"], q.dtype), _e4m3_dequantised(rw, p["v"], q.dtype)
         if dk is None or dv is None:
             continue
@@ -1870,6 +1996,25 @@ def _decode_attn_kv8_impl(q, k8, v8, mask, causal, scale):
 
 
 hip_decode_attn_kv8 = ex.register_operator("hip_decode_attn_kv8", meta=_decode_attn_kv8_meta, fn=_decode_attn_kv8_impl)
+
+
+def _decode_attn_kv8s_meta(q, k8, v8, k_scale, v_scale, mask, causal, scale):
+    return TensorProxy(like=q)
+
+
+def _decode_attn_kv8s_impl(q, k8, v8, k_scale, v_scale, mask, causal, scale):
+    from ..ops.attention import decode_attn, decode_attn_kv8s, decode_attn_kv8s_supported
+    from ..ops.kv8 import dequantise_rows
+
+    if decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale):
+        return decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask, causal, scale)
+    # a head dim the e4m3 kernel does not take: the program as the model spells it
+    return decode_attn(q, dequantise_rows(k8, k_scale, q.dtype), dequantise_rows(v8, v_scale, q.dtype), mask, causal,
+                       scale)
+
+
+hip_decode_attn_kv8s = ex.register_operator("hip_decode_attn_kv8s", meta=_decode_attn_kv8s_meta,
+                                            fn=_decode_attn_kv8s_impl)
 
 
 def _broadcastable(shape, target) -> bool:

@@ -21,6 +21,8 @@ import torch.nn as nn
 import torch.utils.checkpoint
 import torch.nn.functional as F
 
+from ..ops.kv8 import kv8_dequantise_rows, kv8_quantise_rows
+
 
 @dataclass
 class Config:
@@ -209,18 +211,41 @@ class KVCache(nn.Module):
     ``dtype=torch.float8_e4m3fn`` keeps the cache as unscaled, saturating OCP e4m3 in ``uint8``
     buffers (the stored-fp8 convention of ``transforms/fp8_inference.py``): half the bytes per token.
     Writes clamp to +-448 before the cast (torch's cast alone turns larger magnitudes into NaN, the
-    kernels saturate); reads dequantise exactly to the dtype of the incoming k / v."""
+    kernels saturate); reads dequantise exactly to the dtype of the incoming k / v.
 
-    def __init__(self, k_shape, v_shape, device=None, dtype=None):
+    ``scale="row"`` (e4m3 only) adds one power-of-two scale per (token, kv head) row, the format of
+    ``ops/kv8.py``: the buffers ``k_scale`` / ``v_scale`` (uint8 ``[B, n_query_groups, max_seq, 1]``,
+    ``e + 127``, initialised to 127) hold the rows' exponents and the bytes hold ``x * 2^-e``, so the e4m3
+    rounding error is the same relative 2^-4 at every magnitude from 2^-24 to 57344 and no calibration is
+    needed.  ``scale=None`` is the unscaled cache."""
+
+    def __init__(self, k_shape, v_shape, device=None, dtype=None, scale: Optional[str] = None):
         super().__init__()
+        if scale not in (None, "row"):
+            raise ValueError(f"KV cache: scale must be None or 'row', got {scale!r}")
+        if scale is not None and dtype != torch.float8_e4m3fn:
+            raise ValueError(f"KV cache: scale={scale!r} needs dtype=torch.float8_e4m3fn, got {dtype}")
+        self.scale = scale
         if dtype == torch.float8_e4m3fn:
             dtype = torch.uint8
         elif dtype is not None and dtype.is_floating_point and dtype.itemsize == 1:
             raise ValueError(f"KV cache: the only 8-bit float cache is torch.float8_e4m3fn, got {dtype}")
         self.register_buffer("k", torch.zeros(k_shape, device=device, dtype=dtype), persistent=False)
         self.register_buffer("v", torch.zeros(v_shape, device=device, dtype=dtype), persistent=False)
+        if scale is not None:
+            for name, shape in (("k_scale", k_shape), ("v_scale", v_shape)):
+                self.register_buffer(name, torch.full((*shape[:-1], 1), 127, device=device, dtype=torch.uint8),
+                                     persistent=False)
 
     def forward(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        if self.scale is not None:
+            k8, ks = kv8_quantise_rows(k)
+            v8, vs = kv8_quantise_rows(v)
+            k_all = self.k.index_copy_(2, input_pos, k8)
+            v_all = self.v.index_copy_(2, input_pos, v8)
+            ks_all = self.k_scale.index_copy_(2, input_pos, ks)
+            vs_all = self.v_scale.index_copy_(2, input_pos, vs)
+            return kv8_dequantise_rows(k_all, ks_all, k.dtype), kv8_dequantise_rows(v_all, vs_all, v.dtype)
         if self.k.dtype == torch.uint8:
             f8 = torch.float8_e4m3fn
             k8 = k.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
@@ -235,6 +260,9 @@ class KVCache(nn.Module):
     def reset_parameters(self) -> None:
         torch.nn.init.zeros_(self.k)
         torch.nn.init.zeros_(self.v)
+        if self.scale is not None:
+            torch.nn.init.constant_(self.k_scale, 127)
+            torch.nn.init.constant_(self.v_scale, 127)
 
 
 class CausalSelfAttention(nn.Module):
@@ -405,10 +433,14 @@ class GPT(nn.Module):
         self._rope_seq = seq_len
 
     def set_kv_cache(self, batch_size: int, max_seq_length: Optional[int] = None, device=None,
-                     dtype: Optional[torch.dtype] = None) -> None:
+                     dtype: Optional[torch.dtype] = None, scale: Optional[str] = None) -> None:
         """Allocates a static KV cache in every block and the causal mask for incremental decoding.
         ``dtype=torch.float8_e4m3fn`` stores the caches as unscaled, saturating e4m3 in ``uint8`` buffers
-        (see :class:`KVCache`); any other 8-bit float dtype raises ``ValueError``."""
+        (see :class:`KVCache`); any other 8-bit float dtype raises ``ValueError``.  ``scale="row"`` with
+        that dtype adds one power-of-two scale byte per (token, kv head) row; with any other dtype it
+        raises ``ValueError``."""
+        if scale is not None and dtype != torch.float8_e4m3fn:
+            raise ValueError(f"set_kv_cache: scale={scale!r} needs dtype=torch.float8_e4m3fn, got {dtype}")
         c = self.config
         max_seq_length = max_seq_length or c.block_size
         dtype = dtype or self.lm_head.weight.dtype
@@ -418,7 +450,7 @@ class GPT(nn.Module):
             # this rank's kv groups (distributed/tensor_parallel swaps in a localized config)
             ac = getattr(block.attn, "config", c)
             shape = (batch_size, ac.n_query_groups, max_seq_length, ac.head_size)
-            block.attn.kv_cache = KVCache(shape, shape, device=device, dtype=dtype)
+            block.attn.kv_cache = KVCache(shape, shape, device=device, dtype=dtype, scale=scale)
         if self.cos.numel() == 0 or self.cos.shape[0] < max_seq_length:
             self.set_rope_cache(max_seq_length, device=device)
         ones = torch.ones((max_seq_length, max_seq_length), device=device, dtype=torch.bool)

@@ -403,7 +403,9 @@ def decode_launch_shape(rows: int, S: int):
     return wsplit, nsplit, chunk
 
 
-def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None):
+def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None, scales=None):
+    """One launch of ``entry``; ``scales`` = (k_scale, v_scale) for the scaled-e4m3 entry, whose argument
+    list carries the two pointers after v and their (b, h, s) strides after the mask's."""
     lib = require()
     B, Hq, T, D = q.shape
     Hkv, S = k.shape[1], k.shape[2]
@@ -420,12 +422,14 @@ def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None)
     if nsplit > 1:
         ws_acc = torch.empty((nsplit, rows, D), device=q.device, dtype=torch.float32)
         ws_ml = torch.empty((nsplit, rows, 2), device=q.device, dtype=torch.float32)
-    st = (ctypes.c_int64 * 13)(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
-                               v.stride(0), v.stride(1), v.stride(2), *ms)
+    extra = () if scales is None else (*scales[0].stride()[:3], *scales[1].stride()[:3])
+    st = (ctypes.c_int64 * (13 + len(extra)))(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
+                                              k.stride(2), v.stride(0), v.stride(1), v.stride(2), *ms, *extra)
     mptr = None if mask is None else mask.data_ptr()
-    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), mptr, ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq, Hkv, T, S, D,
-                             ctypes.cast(st, ctypes.c_void_p), chunk, nsplit, int(causal), float(sc), int(wsplit),
-                             stream_ptr(q.device))
+    sptrs = () if scales is None else (ptr(scales[0]), ptr(scales[1]))
+    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *sptrs, mptr, ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq, Hkv,
+                             T, S, D, ctypes.cast(st, ctypes.c_void_p), chunk, nsplit, int(causal), float(sc),
+                             int(wsplit), stream_ptr(q.device))
     check(rc, entry)
     return o
 
@@ -465,3 +469,35 @@ def decode_attn_kv8(q, k8, v8, mask=None, causal: bool = False, scale: float | N
                          f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}")
     q, k8, v8 = _aligned_rows(q), _rows8_in_place(k8), _rows8_in_place(v8)
     return _decode_launch("lta_decode_attn_kv8", q, k8, v8, mask, causal, scale)
+
+
+register_signature("lta_decode_attn_kv8s", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                            c_int, c_int, c_float, c_int, c_void_p])
+
+
+def decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale) -> bool:
+    """What the scaled-e4m3 decode kernel takes: the operands of ``decode_attn_kv8`` plus uint8 scale
+    caches [B, Hkv, S, 1] on the same device (any strides: a lane loads single bytes)."""
+    if not decode_attn_kv8_supported(q, k8, v8):
+        return False
+    for s in (k_scale, v_scale):
+        if s is None or s.dtype != torch.uint8 or s.device != k8.device or s.dim() != 4:
+            return False
+        if tuple(s.shape) != (*k8.shape[:3], 1):
+            return False
+    return True
+
+
+def decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask=None, causal: bool = False, scale: float | None = None):
+    """``decode_attn`` over the scaled e4m3 cache of ``ops/kv8.py``: k8 / v8 uint8 [B, Hkv, S, D], k_scale /
+    v_scale uint8 [B, Hkv, S, 1] (``e + 127`` per row).  Equals ``decode_attn`` over
+    ``dequantise_rows(k8, k_scale, q.dtype)`` / ``dequantise_rows(v8, v_scale, q.dtype)`` bit for bit (fp32
+    subnormal or overflowing partial sums aside); the scales are read in place."""
+    if not decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale):
+        raise ValueError(f"decode_attn_kv8s: unsupported operands q {q.dtype} {tuple(q.shape)}, "
+                         f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, scales "
+                         f"{None if k_scale is None else (k_scale.dtype, tuple(k_scale.shape))} / "
+                         f"{None if v_scale is None else (v_scale.dtype, tuple(v_scale.shape))}")
+    q, k8, v8 = _aligned_rows(q), _rows8_in_place(k8), _rows8_in_place(v8)
+    return _decode_launch("lta_decode_attn_kv8s", q, k8, v8, mask, causal, scale, scales=(k_scale, v_scale))

@@ -51,19 +51,40 @@ constexpr float kSumStart = sizeof(KV) == 1 ? -0.f : 0.f;
 
 // acc / l rounded to T.  For the e4m3 kernels the product first settles in a register: hipcc otherwise folds
 // the multiply and the fp16 conversion into one v_fma_mixlo_f16 (x * y + 0), and the + 0 turns a -0 into +0.
-template <typename T, typename KV>
+// The scaled e4m3 kernels (KS) are held bit for bit to the 16-bit kernel over the dequantised cache, so they
+// convert as that kernel does: in fp16 the fold is a single rounding of acc * inv, the settled product a
+// double one (fp32, then fp16), and the two differ in about one element in 10^5.
+template <typename T, typename KV, bool KS = false>
 __device__ __forceinline__ T normalised(float acc, float inv) {
   float r = acc * inv;
-  if constexpr (sizeof(KV) == 1) asm volatile("" : "+v"(r));
+  if constexpr (sizeof(KV) == 1 && !KS) asm volatile("" : "+v"(r));
   return from_f32<T>(r);
 }
 
-template <typename T, typename KV, int D, bool WSPLIT>
+// Scaled e4m3 cache (ops/kv8.py): one byte e + 127 per (b, kv head, key) row of K and of V; the row's
+// values are its bytes times 2^e.  Strides in bytes over b, h, s.
+struct KVScales {
+  const uint8_t *k, *v;
+  int64_t ksb, ksh, kss, vsb, vsh, vss;
+};
+struct NoScales {};
+
+// KS (with KV = uint8_t): the cache is the scaled one.  The lane that owns key j loads that key's two scale
+// bytes (consecutive bytes across the lanes of a 64-key block) and forms 2^e as byte << 23; the score is
+// dot * 2^ek and V is accumulated with p * 2^ev in place of p, while l keeps the unscaled p.  Both products
+// are exact, and scaling an operand by a power of two commutes with the rounding of every fmaf, so the
+// result equals the 16-bit kernel's over the dequantised cache bit for bit.  The claim excludes fp32
+// subnormals and overflow (a partial sum below 2^-126 or above 2^127 after scaling rounds differently), and
+// an all-zero result (the sums start from the e4m3 kernels' -0).  A contraction of dot * 2^ek into the following subtraction
+// (v_fma) is harmless for the same reason: the product it skips rounding is exact.
+template <typename T, typename KV, int D, bool WSPLIT, bool KS = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const T* __restrict__ q, const KV* __restrict__ k, const KV* __restrict__ v, const uint8_t* __restrict__ mask,
     T* __restrict__ o, float* __restrict__ ws_acc, float* __restrict__ ws_ml, int B, int Hq, int Hkv, int Tq, int S,
     int64_t qsb, int64_t qsh, int64_t qst, int64_t ksb, int64_t ksh, int64_t kss, int64_t vsb, int64_t vsh,
-    int64_t vss, int64_t msb, int64_t msh, int64_t mst, int64_t mss, int chunk, int causal, float scale) {
+    int64_t vss, int64_t msb, int64_t msh, int64_t mst, int64_t mss, int chunk, int causal, float scale,
+    std::conditional_t<KS, KVScales, NoScales> sc) {
+  static_assert(!KS || sizeof(KV) == 1, "scales belong to an e4m3 cache");
   constexpr int DPL = D / 64;          // output dims per lane after the final reduce-scatter
   constexpr bool kE4M3 = sizeof(KV) == 1;
   constexpr int NV = 16 / sizeof(KV);  // elements per 16-byte load
@@ -88,6 +109,12 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   const KV* kbase = k + b * ksb + hk * ksh;
   const KV* vbase = v + b * vsb + hk * vsh;
   const uint8_t* mrow = mask ? mask + b * msb + hq * msh + t * mst : nullptr;
+  [[maybe_unused]] const uint8_t* ksrow = nullptr;
+  [[maybe_unused]] const uint8_t* vsrow = nullptr;
+  if constexpr (KS) {
+    ksrow = sc.k + b * sc.ksb + hk * sc.ksh;
+    vsrow = sc.v + b * sc.vsb + hk * sc.vsh;
+  }
 
   // every lane owns one key per 64-key block: QK and PV are both lane-parallel; the per-lane
   // partial outputs acc[D] are reduce-scattered across the wave once at the end.
@@ -102,7 +129,13 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     if (valid && mrow) valid = mrow[(int64_t)j * mss] != 0;
     if (!__any(valid)) continue;  // fully masked block: no K/V traffic
     float s = -INFINITY;
+    // scale bytes of key j's K row and V row: loaded ahead of the K row, turned into 2^e where first used
+    [[maybe_unused]] uint32_t kb = 127, vb = 127;
     if (valid) {
+      if constexpr (KS) {
+        kb = ksrow[(int64_t)j * sc.kss];
+        vb = vsrow[(int64_t)j * sc.vss];
+      }
       const KV* krow = kbase + (int64_t)j * kss;
       float dot = 0.f;
 #pragma unroll
@@ -119,6 +152,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
         }
       }
       s = dot;
+      if constexpr (KS) s = dot * __uint_as_float(kb << 23);
     }
     const float m_new = fmaxf(m, wave_max(s));
     const float p = valid ? __expf(s - m_new) : 0.f;
@@ -127,9 +161,15 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     m = m_new;
     if (valid) {
       const KV* vrow = vbase + (int64_t)j * vss;
+      [[maybe_unused]] const float pv = p * __uint_as_float(vb << 23);
 #pragma unroll
       for (int d = 0; d < D; d += NV) {
-        if constexpr (kE4M3) {
+        if constexpr (KS) {
+          float x[NV];
+          load16_e4m3(vrow + d, x);
+#pragma unroll
+          for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(pv, x[e], acc[d + e] * corr);
+        } else if constexpr (kE4M3) {
           float x[NV];
           load16_e4m3(vrow + d, x);
 #pragma unroll
@@ -191,7 +231,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     const float inv = 1.f / l;  // fully masked row -> 0 * inf = nan, like PyTorch SDPA
     T* orow = o + (((int64_t)b * Hq + hq) * Tq + t) * D + lane * DPL;  // o is [B, Hq, Tq, D]
 #pragma unroll
-    for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV>(acc[i], inv);
+    for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
   } else {
     float* wa = ws_acc + ((int64_t)split * rows + row) * D + lane * DPL;
 #pragma unroll
@@ -203,7 +243,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   }
 }
 
-template <typename T, typename KV, int D>
+template <typename T, typename KV, int D, bool KS = false>
 __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __restrict__ ws_acc,
                                                                  const float* __restrict__ ws_ml, T* __restrict__ o,
                                                                  int rows, int nsplit, int Hq, int Tq) {
@@ -227,28 +267,28 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   const float inv = 1.f / L;
   T* orow = o + (((int64_t)b * Hq + hq) * Tq + t) * D + lane * DPL;
 #pragma unroll
-  for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV>(acc[i], inv);
+  for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
 }
 
-template <typename T, typename KV, int D>
+template <typename T, typename KV, int D, bool KS = false>
 int launch(const void* q, const void* k, const void* v, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
            int Hq, int Hkv, int Tq, int S, const int64_t* st, int chunk, int nsplit, int causal, float scale,
-           int wsplit, hipStream_t stream) {
+           int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc = {}) {
   const int rows = B * Tq * Hq;
   if (wsplit) {
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
                        (const KV*)k, (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
                        Tq, S, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11],
-                       st[12], chunk, causal, scale);
+                       st[12], chunk, causal, scale, sc);
   } else {
     dim3 grid((rows + kRowsPerBlock - 1) / kRowsPerBlock, nsplit);
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
                        (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
                        st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12],
-                       chunk, causal, scale);
+                       chunk, causal, scale, sc);
   }
   if (nsplit > 1)
-    hipLaunchKernelGGL((decode_attn_combine_kernel<T, KV, D>), dim3(rows), dim3(64), 0, stream, (const float*)ws_acc,
+    hipLaunchKernelGGL((decode_attn_combine_kernel<T, KV, D, KS>), dim3(rows), dim3(64), 0, stream, (const float*)ws_acc,
                        (const float*)ws_ml, (T*)o, rows, nsplit, Hq, Tq);
   return (int)hipGetLastError();
 }
@@ -292,6 +332,31 @@ LTA_EXPORT int lta_decode_attn_kv8(int dtype, const void* q, const void* k, cons
   } else if (dtype == kF16) {
     if (D == 64) return launch<__half, uint8_t, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
     if (D == 128) return launch<__half, uint8_t, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
+  }
+  return (int)hipErrorInvalidValue;
+}
+
+// The same launch over the scaled e4m3 cache of ops/kv8.py: k / v as for lta_decode_attn_kv8, k_scale / v_scale
+// uint8 [B, Hkv, S, 1] holding e + 127 per row; strides[13..18] are theirs (bytes): k scale b,h,s | v scale b,h,s.
+LTA_EXPORT int lta_decode_attn_kv8s(int dtype, const void* q, const void* k, const void* v, const void* k_scale,
+                                    const void* v_scale, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
+                                    int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int chunk, int nsplit,
+                                    int causal, float scale, int wsplit, void* stream) {
+  using namespace lta;
+  hipStream_t s = (hipStream_t)stream;
+  if (Hkv <= 0 || Hq % Hkv != 0 || chunk <= 0 || nsplit <= 0) return (int)hipErrorInvalidValue;
+  if (k_scale == nullptr || v_scale == nullptr) return (int)hipErrorInvalidValue;
+  for (int i = 3; i < 9; ++i)
+    if (strides[i] % 16) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)k | (uintptr_t)v) % 16) return (int)hipErrorInvalidValue;
+  const KVScales sc{(const uint8_t*)k_scale, (const uint8_t*)v_scale, strides[13], strides[14], strides[15],
+                    strides[16], strides[17], strides[18]};
+  if (dtype == kBF16) {
+    if (D == 64) return launch<__hip_bfloat16, uint8_t, 64, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
+    if (D == 128) return launch<__hip_bfloat16, uint8_t, 128, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
+  } else if (dtype == kF16) {
+    if (D == 64) return launch<__half, uint8_t, 64, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
+    if (D == 128) return launch<__half, uint8_t, 128, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
   }
   return (int)hipErrorInvalidValue;
 }

@@ -158,15 +158,51 @@ __device__ __forceinline__ void store8_e4m3(uint8_t* p, const Vec16<T>& x) {
   *reinterpret_cast<uint2*>(p) = w;
 }
 
+// Scaled e4m3 cache (ops/kv8.py): where the scale byte of a k / v head row goes, as KVDst for the rows.
+struct ScaleDst {
+  uint8_t *k, *v;
+  int64_t ksb, ksg, kss, vsb, vsg, vss;
+};
+struct NoScale {};
+
+// One k / v head row of a scaled e4m3 cache.  The row's 2 << pair_shift chunks sit in 1 << pair_shift
+// consecutive lanes of one wave, a group aligned to its size and either wholly active or wholly inactive
+// (all its lanes share h, and the item loop's bound is a multiple of the group), so the xor shuffles below
+// read active lanes only.  amax of the values already rounded to T -> e = the smallest exponent in
+// [-15, 7] with amax * 2^-e <= 448 (integer formula of ops/kv8.py; fmaxf drops a NaN, see there) ->
+// bytes of x * 2^-e (exact product, then the saturating conversion) and the byte e + 127.
+template <typename T>
+__device__ __forceinline__ void store_row_e4m3_scaled(uint8_t* row, uint8_t* scale, int d0, int half, int pair_shift,
+                                                      const Vec16<T>& a, const Vec16<T>& b) {
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fmaxf(fabsf(to_f32(a.v[j])), fabsf(to_f32(b.v[j]))));
+  for (int off = 1; off < (1 << pair_shift); off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  const uint32_t bits = __float_as_uint(m);  // m >= 0: no sign bit
+  int e = (int)(bits >> 23) - 135 + ((bits & 0x7FFFFFu) > 0x600000u ? 1 : 0);
+  e = min(max(e, -15), 7);
+  const float inv = __uint_as_float((uint32_t)(127 - e) << 23);  // 2^-e
+  uint2 w0, w1;
+  w0.x = cvt4<false>(to_f32(a.v[0]) * inv, to_f32(a.v[1]) * inv, to_f32(a.v[2]) * inv, to_f32(a.v[3]) * inv);
+  w0.y = cvt4<false>(to_f32(a.v[4]) * inv, to_f32(a.v[5]) * inv, to_f32(a.v[6]) * inv, to_f32(a.v[7]) * inv);
+  w1.x = cvt4<false>(to_f32(b.v[0]) * inv, to_f32(b.v[1]) * inv, to_f32(b.v[2]) * inv, to_f32(b.v[3]) * inv);
+  w1.y = cvt4<false>(to_f32(b.v[4]) * inv, to_f32(b.v[5]) * inv, to_f32(b.v[6]) * inv, to_f32(b.v[7]) * inv);
+  *reinterpret_cast<uint2*>(row + d0) = w0;
+  *reinterpret_cast<uint2*>(row + d0 + half) = w1;
+  if (d0 == 0) *scale = (uint8_t)(e + 127);  // the group's first lane
+}
+
 // KT: the element type of the forward's k / v destination, T or uint8_t (an unscaled e4m3 cache: the
-// row rounded to T as for a T cache, then converted, so the launch equals RoPE + clamp + cast + copy)
-template <typename T, typename C, bool BWD, typename KT = T>
+// row rounded to T as for a T cache, then converted, so the launch equals RoPE + clamp + cast + copy).
+// KS: the uint8_t cache is the scaled one, one power-of-two scale byte per head row through `sd`.
+template <typename T, typename C, bool BWD, typename KT = T, bool KS = false>
 __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__ in0, const T* __restrict__ in1,
                                                            const T* __restrict__ in2, const C* __restrict__ cos_,
                                                            const C* __restrict__ sin_, T* __restrict__ out0,
                                                            KT* __restrict__ out1, KT* __restrict__ out2,
                                                            const int64_t* __restrict__ pos, KVDst st, int Tn, int nh,
-                                                           int ng, int hs, int pair_shift) {
+                                                           int ng, int hs, int pair_shift,
+                                                           std::conditional_t<KS, ScaleDst, NoScale> sd) {
   // fwd: in0 = qkv, out0/1/2 = q/k/v (k/v through st); bwd: in0/1/2 = dq/dk/dv, out0 = dqkv
   constexpr int VW = 8;
   constexpr bool kE4M3 = !BWD && sizeof(KT) == 1;
@@ -181,6 +217,7 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
     const T* src;
     T* dst;
     [[maybe_unused]] uint8_t* kv8 = nullptr;  // e4m3 cache: the row of a k / v head (dst unused for it)
+    [[maybe_unused]] uint8_t* sc8 = nullptr;  // scaled e4m3 cache: that row's scale byte
     if constexpr (!BWD) {
       src = in0 + ((int64_t)row * heads + h) * hs;
       if (h < nh) {
@@ -191,6 +228,9 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
           dst = nullptr;
           kv8 = h < nh + ng ? out1 + b * st.ksb + (h - nh) * st.ksg + s * st.kss
                             : out2 + b * st.vsb + (h - nh - ng) * st.vsg + s * st.vss;
+          if constexpr (KS)
+            sc8 = h < nh + ng ? sd.k + b * sd.ksb + (h - nh) * sd.ksg + s * sd.kss
+                              : sd.v + b * sd.vsb + (h - nh - ng) * sd.vsg + s * sd.vss;
         } else {
           dst = h < nh + ng ? out1 + b * st.ksb + (h - nh) * st.ksg + s * st.kss
                             : out2 + b * st.vsb + (h - nh - ng) * st.vsg + s * st.vss;
@@ -204,7 +244,9 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
     }
     const Vec16<T> x1 = load16(src + d0), x2 = load16(src + d0 + half);
     if (h >= nh + ng) {  // v: layout change only
-      if constexpr (kE4M3) {
+      if constexpr (KS) {
+        store_row_e4m3_scaled(kv8, sc8, d0, half, pair_shift, x1, x2);
+      } else if constexpr (kE4M3) {
         store8_e4m3(kv8 + d0, x1);
         store8_e4m3(kv8 + d0 + half, x2);
       } else {
@@ -232,8 +274,12 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
     }
     if constexpr (kE4M3) {
       if (kv8 != nullptr) {
-        store8_e4m3(kv8 + d0, o1);
-        store8_e4m3(kv8 + d0 + half, o2);
+        if constexpr (KS) {
+          store_row_e4m3_scaled(kv8, sc8, d0, half, pair_shift, o1, o2);
+        } else {
+          store8_e4m3(kv8 + d0, o1);
+          store8_e4m3(kv8 + d0 + half, o2);
+        }
         continue;
       }
     }
@@ -286,7 +332,8 @@ static int qkv_rope_fwd_launch(int dtype, int cdtype, const void* qkv, const voi
     LTA_DISPATCH_TC(dtype, cdtype,
                     hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false>), dim3(B * Tn), dim3(256), 0, stream,
                                        (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
-                                       (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, Tn, nh, ng, hs, sh));
+                                       (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, Tn, nh, ng, hs, sh,
+                                       NoScale{}));
     return (int)hipGetLastError();
   }
   const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));
@@ -332,7 +379,35 @@ LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8(int dtype, int cdtype, const void* qkv
     using C = decltype(c);
     hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t>), dim3(B * Tn), dim3(256), 0, stream, (const T*)qkv,
                        (const T*)nullptr, (const T*)nullptr, (const C*)cos_, (const C*)sin_, (T*)q, (uint8_t*)kc,
-                       (uint8_t*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs, sh);
+                       (uint8_t*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs, sh, NoScale{});
+    return (int)hipGetLastError();
+  };
+  if (dtype == kBF16 && cdtype == kF32) return launch(__hip_bfloat16{}, float{});
+  if (dtype == kBF16 && cdtype == kBF16) return launch(__hip_bfloat16{}, __hip_bfloat16{});
+  if (dtype == kF16 && cdtype == kF32) return launch(__half{}, float{});
+  if (dtype == kF16 && cdtype == kF16) return launch(__half{}, __half{});
+  return -1;
+}
+
+// As lta_qkv_rope_cache_fwd_kv8 for the scaled e4m3 cache of ops/kv8.py: every k / v head row is stored as
+// the bytes of x * 2^-e plus one scale byte e + 127 in ksc / vsc [B, ng, S, 1] (uint8).  `strides`: k b,g,s |
+// v b,g,s | k scale b,g,s | v scale b,g,s.  A head row must fit one wave's lanes (hs <= 1024).
+LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
+                                           void* q, void* kc, void* vc, void* ksc, void* vsc, const void* pos,
+                                           const int64_t* strides, int B, int Tn, int nh, int ng, int hs, int rope_n,
+                                           hipStream_t stream) {
+  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
+  if (((uintptr_t)kc | (uintptr_t)vc) % 8) return -2;
+  const int sh = row_pair_shift(dtype, hs, rope_n);
+  if (sh < 0 || sh > 6 || dtype == kF32) return -2;
+  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  const ScaleDst sd{(uint8_t*)ksc, (uint8_t*)vsc, strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
+  auto launch = [&](auto t, auto c) {
+    using T = decltype(t);
+    using C = decltype(c);
+    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, true>), dim3(B * Tn), dim3(256), 0, stream,
+                       (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_, (const C*)sin_, (T*)q,
+                       (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs, sh, sd);
     return (int)hipGetLastError();
   };
   if (dtype == kBF16 && cdtype == kF32) return launch(__hip_bfloat16{}, float{});
@@ -352,7 +427,7 @@ LTA_EXPORT int lta_qkv_rope_bwd(int dtype, int cdtype, const void* dq, const voi
                     hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, true>), dim3(B * Tn), dim3(256), 0, stream,
                                        (const T*)dq, (const T*)dk, (const T*)dv, (const C*)cos_, (const C*)sin_,
                                        (T*)dqkv, (T*)nullptr, (T*)nullptr, (const int64_t*)nullptr, KVDst{0, 0, 0, 0, 0, 0},
-                                       Tn, nh, ng, hs, sh));
+                                       Tn, nh, ng, hs, sh, NoScale{}));
     return (int)hipGetLastError();
   }
   const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));

@@ -14,6 +14,9 @@ register_signature("lta_qkv_rope_cache_fwd", [c_int, c_int, c_void_p, c_void_p, 
 register_signature("lta_qkv_rope_cache_fwd_kv8", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                                   c_void_p])
+register_signature("lta_qkv_rope_cache_fwd_kv8s", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                   c_int, c_int, c_int, c_void_p])
 register_signature("lta_qkv_rope_bwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
 register_signature("lta_swiglu_fwd", [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -80,11 +83,37 @@ def qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups: int, head_size: i
     return pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == T and pos.is_contiguous()
 
 
-def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kc, vc, pos):
+def qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_groups: int, head_size: int,
+                                    rope_n: int | None = None) -> bool:
+    """What the scaled e4m3 write takes: uint8 caches as ``qkv_rope_cache_supported`` has them, a head row
+    within one wave (``head_size <= 1024``), and uint8 scale caches [B, ng, S, 1] over the same rows."""
+    if kc.dtype != torch.uint8 or vc.dtype != torch.uint8 or head_size > 1024:
+        return False
+    if not qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size, rope_n):
+        return False
+    for s, c in ((k_scale, kc), (v_scale, vc)):
+        if s is None or s.dtype != torch.uint8 or s.device != c.device or s.dim() != 4:
+            return False
+        if tuple(s.shape) != (*c.shape[:3], 1):
+            return False
+    return True
+
+
+def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kc, vc, pos,
+                       k_scale=None, v_scale=None):
     """qkv split + RoPE with k / v written in place into the static caches ``kc`` / ``vc`` at rows
     ``pos`` (the decode step's ``index_copy_`` fused into the same launch).  Returns (q, kc, vc).
     uint8 caches receive the rows as unscaled saturating e4m3: bit for bit
-    ``k.clamp(-448, 448).to(float8_e4m3fn).view(uint8)`` of ``qkv_rope_fwd``'s k (and v)."""
+    ``k.clamp(-448, 448).to(float8_e4m3fn).view(uint8)`` of ``qkv_rope_fwd``'s k (and v).
+    With ``k_scale`` / ``v_scale`` (uint8 [B, ng, S, 1]) the caches are the scaled ones of ``ops/kv8.py``:
+    bytes and scale bytes equal ``quantise_rows`` of ``qkv_rope_fwd``'s k (and v) bit for bit, and the
+    result is (q, kc, vc, k_scale, v_scale)."""
+    if (k_scale is None) != (v_scale is None):
+        raise ValueError("qkv_rope_cache_fwd: k_scale and v_scale come together")
+    if k_scale is not None and not qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_groups,
+                                                                   head_size, rope_n):
+        raise ValueError("qkv_rope_cache_fwd: operands the scaled e4m3 write does not take "
+                         "(see qkv_rope_cache_scaled_supported)")
     lib = require()
     qkv = _c(qkv)
     B, T, _ = qkv.shape
@@ -95,8 +124,15 @@ def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_siz
     if cos.dtype not in (torch.float32, qkv.dtype):
         cos, sin = cos.float(), sin.float()
     q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
+    if k_scale is not None:
+        st = (ctypes.c_int64 * 12)(*kc.stride()[:3], *vc.stride()[:3], *k_scale.stride()[:3], *v_scale.stride()[:3])
+        rc = lib.lta_qkv_rope_cache_fwd_kv8s(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), ptr(kc),
+                                             ptr(vc), ptr(k_scale), ptr(v_scale), ptr(pos), st, B, T, n_head,
+                                             n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
+        check(rc, "lta_qkv_rope_cache_fwd_kv8s")
+        return q, kc, vc, k_scale, v_scale
     st = (ctypes.c_int64 * 6)(*kc.stride()[:3], *vc.stride()[:3])
-    entry = "lta_qkv_rope_cache_fwd_kv8" if kc.dtype == torch.uint8 else "lta_qkv_rope_cache_fwd"
+    entry ="lta_qkv_rope_cache_fwd_kv8" if kc.dtype == torch.uint8 else "lta_qkv_rope_cache_fwd"
     rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), ptr(kc), ptr(vc),
                              ptr(pos), st, B, T, n_head, n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
     check(rc, entry)
