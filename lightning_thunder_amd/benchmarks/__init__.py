@@ -7,3 +7,10 @@ the HF ``generate`` quickstart ``examples/quickstart/hf_llm.py``).
 * ``python -m lightning_thunder_amd.benchmarks.targets``: per-component micro-benchmarks (NanoGPT GPT-2
   block, LitGPT QKV-split+RoPE, RMSNorm, SDPA, cross-entropy) fwd/bwd, eager vs compiled.
 """
+import torch
+
+# --kv-cache-dtype -> set_kv_cache's keywords: "model" keeps the cache in the model's dtype, "fp8" stores
+# unscaled e4m3 (half the bytes), "fp8-row" e4m3 with one power-of-two scale byte per (token, kv head) row
+KV_CACHE_FORMATS = {"model": {"dtype": torch.bfloat16, "scale": None},
+                    "fp8": {"dtype": torch.float8_e4m3fn, "scale": None},
+                    "fp8-row": {"dtype": torch.float8_e4m3fn, "scale": "row"}}

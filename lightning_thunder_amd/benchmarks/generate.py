@@ -29,11 +29,7 @@ import time
 
 import torch
 
-
-# --kv-cache-dtype: "model" keeps the cache in the model's dtype, "fp8" stores unscaled e4m3 (half the bytes),
-# "fp8-row" e4m3 with one power-of-two scale byte per (token, kv head) row (set_kv_cache(..., scale="row"))
-KV_CACHE_DTYPES = {"model": torch.bfloat16, "fp8": torch.float8_e4m3fn, "fp8-row": torch.float8_e4m3fn}
-KV_CACHE_SCALES = {"model": None, "fp8": None, "fp8-row": "row"}
+from . import KV_CACHE_FORMATS
 
 
 def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model"):
@@ -48,8 +44,7 @@ def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: 
     init_weights(model)
     model.requires_grad_(False)
     model.eval()
-    model.set_kv_cache(1, max_seq, device=device, dtype=KV_CACHE_DTYPES[kv_cache_dtype],
-                       scale=KV_CACHE_SCALES[kv_cache_dtype])
+    model.set_kv_cache(1, max_seq, device=device, **KV_CACHE_FORMATS[kv_cache_dtype])
     return model, cfg
 
 
@@ -169,7 +164,7 @@ def main(argv=None):
     p.add_argument("--temperature", type=float, default=0.0, help="> 0: sample (LitGPT modes only) instead of greedy")
     p.add_argument("--top-k", type=int, default=None)
     p.add_argument("--top-p", type=float, default=None)
-    p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_DTYPES), default="model",
+    p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_FORMATS), default="model",
                    help="LitGPT modes: 'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes), "
                         "'fp8-row' as e4m3 with one power-of-two scale byte per (token, kv head) row")
     p.add_argument("--seed", type=int, default=0, help="torch.manual_seed before every sampled generation")

@@ -25,16 +25,12 @@ import time
 
 import torch
 
+from . import KV_CACHE_FORMATS
+
 
 def _percentile(xs, q):
     s = sorted(xs)
     return s[min(len(s) - 1, int(round(q * (len(s) - 1))))]
-
-
-# --kv-cache-dtype: "model" keeps the cache in the model's dtype, "fp8" stores unscaled e4m3 (half the bytes),
-# "fp8-row" e4m3 with one power-of-two scale byte per (token, kv head) row (set_kv_cache(..., scale="row"))
-KV_CACHE_DTYPES = {"model": torch.bfloat16, "fp8": torch.float8_e4m3fn, "fp8-row": torch.float8_e4m3fn}
-KV_CACHE_SCALES = {"model": None, "fp8": None, "fp8-row": "row"}
 
 
 def _build(args, device):
@@ -50,7 +46,7 @@ def _build(args, device):
     model.requires_grad_(False)
     model.eval()
     model.set_kv_cache(args.batch_size, args.input_length + args.output_length + 8, device=device,
-                       dtype=KV_CACHE_DTYPES[args.kv_cache_dtype], scale=KV_CACHE_SCALES[args.kv_cache_dtype])
+                       **KV_CACHE_FORMATS[args.kv_cache_dtype])
     return model, cfg
 
 
@@ -144,7 +140,7 @@ def main(argv=None):
     p.add_argument("--warmup-iterations", type=int, default=2)
     p.add_argument("--modes", default="eager,thunder,hipgraph")
     p.add_argument("--n-layer", type=int, default=None, help="debug only")
-    p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_DTYPES), default="model",
+    p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_FORMATS), default="model",
                    help="'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes), 'fp8-row' as e4m3 "
                         "with one power-of-two scale byte per (token, kv head) row")
     args = p.parse_args(argv)

@@ -18,6 +18,7 @@ from ..core.prims import OpTags
 from ..core.proxies import TensorProxy, pyval
 from ..core import dtypes
 from ..extend import OperatorExecutor, register_executor, add_default_executor
+from ..ops.kv8 import E4M3_MAX
 from .rewrite import Rewrite, operands
 
 ex = OperatorExecutor("hipex", version="0.1")
@@ -912,32 +913,34 @@ def _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_
     return TensorProxy(like=qkv, shape=(B, n_head, T, head_size)), TensorProxy(like=kc), TensorProxy(like=vc)
 
 
-def _e4m3_bytes(t):
-    """The stored form of an unscaled e4m3 KV cache row: saturate, round to nearest even, as bytes."""
-    return t.clamp(-_E4M3_MAX, _E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+def _qkv_rope_cache_run(rope_args, caches, pos, supported, stored):
+    """The cache-writing RoPE over ``caches`` in operator order (kc, vc, then scale caches): the kernel
+    where ``supported`` takes the operands, else the program as the model spells it, with ``stored(t)``
+    the tensors k (or v) goes into its caches as."""
+    from ..ops.fused import qkv_rope_cache_fwd, qkv_rope_fwd
+
+    if supported(rope_args[0], *caches, pos, *rope_args[4:]):
+        return qkv_rope_cache_fwd(*rope_args, *caches[:2], pos, *caches[2:])
+    q, k, v = qkv_rope_fwd(*rope_args)
+    pos = pos if pos.dtype == torch.int64 else pos.long()  # index_copy_ takes int64 indices only
+    srcs = (t for pair in zip(stored(k), stored(v)) for t in pair)
+    return (q, *(c.index_copy_(2, pos, t) for c, t in zip(caches, srcs)))
 
 
 def _qkv_rope_cache_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
-    from ..ops.fused import qkv_rope_cache_fwd, qkv_rope_cache_supported, qkv_rope_fwd
+    from ..ops.fused import qkv_rope_cache_supported
+    from ..ops.kv8 import e4m3_bytes
 
     kv8 = kc.dtype == torch.uint8  # unscaled e4m3 caches (models/litgpt.py KVCache)
     if kv8 != (vc.dtype == torch.uint8):
         raise ValueError("hip_qkv_rope_cache: one of the two caches is uint8 (e4m3), the other is not")
-    if qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size, rope_n):
-        return qkv_rope_cache_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos)
-    q, k, v = qkv_rope_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
-    pos = pos if pos.dtype == torch.int64 else pos.long()  # index_copy_ takes int64 indices only
-    if kv8:
-        k, v = _e4m3_bytes(k), _e4m3_bytes(v)
-    return q, kc.index_copy_(2, pos, k), vc.index_copy_(2, pos, v)
+    return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n), (kc, vc), pos,
+                               qkv_rope_cache_supported, (lambda t: (e4m3_bytes(t),)) if kv8 else (lambda t: (t,)))
 
 
 hip_qkv_rope_cache = ex.register_operator("hip_qkv_rope_cache", meta=_qkv_rope_cache_meta, fn=_qkv_rope_cache_impl,
                                           tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
 hip_qkv_rope_cache.written_args = (7, 8)  # kc, vc; qkv/cos/sin/pos are only read
-
-
-_E4M3_MAX = 448.0
 
 
 # the scaled e4m3 cache (ops/kv8.py): bytes and one scale byte per (token, kv head) row, all four written
@@ -948,18 +951,11 @@ def _qkv_rope_cache_s8_meta(qkv, cos, sin, n_head, n_query_groups, head_size, ro
 
 
 def _qkv_rope_cache_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, k_scale, v_scale, pos):
-    from ..ops.fused import qkv_rope_cache_fwd, qkv_rope_cache_scaled_supported, qkv_rope_fwd
+    from ..ops.fused import qkv_rope_cache_scaled_supported
     from ..ops.kv8 import quantise_rows
 
-    if qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_groups, head_size, rope_n):
-        return qkv_rope_cache_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos,
-                                  k_scale=k_scale, v_scale=v_scale)
-    # a shape the row kernel does not take: the program as the model spells it
-    q, k, v = qkv_rope_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
-    pos = pos if pos.dtype == torch.int64 else pos.long()
-    (k8, ks), (v8, vs) = quantise_rows(k), quantise_rows(v)
-    return (q, kc.index_copy_(2, pos, k8), vc.index_copy_(2, pos, v8), k_scale.index_copy_(2, pos, ks),
-            v_scale.index_copy_(2, pos, vs))
+    return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n),
+                               (kc, vc, k_scale, v_scale), pos, qkv_rope_cache_scaled_supported, quantise_rows)
 
 
 hip_qkv_rope_cache_s8 = ex.register_operator("hip_qkv_rope_cache_s8", meta=_qkv_rope_cache_s8_meta,
@@ -989,7 +985,7 @@ def _e4m3_quantise_chain(rw, t):
     uint8 tensor is the last one's output.  None for anything else: other bounds, no clamp or another
     fp8 format would give other bytes than the kernel's saturating e4m3 conversion."""
     chain = []
-    for names, rest in ((("clamp", "torch_clamp"), (-_E4M3_MAX, _E4M3_MAX)),
+    for names, rest in ((("clamp", "torch_clamp"), (-E4M3_MAX, E4M3_MAX)),
                         (("to", "torch_to"), (torch.float8_e4m3fn,)),
                         (("view", "torch_view"), (torch.uint8,))):
         if rw.uses(t) != 1:
@@ -1011,58 +1007,24 @@ def _e4m3_quantise_chain(rw, t):
     return chain
 
 
-def _fuse_scaled_kv_cache_write(rw, i, ik, iv) -> None:
-    """The scaled e4m3 cache's write behind the ``hip_qkv_rope`` at ``i``: ``k8, ks = kv8_quantise_rows(k)``
-    at ``ik`` and the same for v at ``iv``, each of the four results read once, by an
-    ``index_copy_inplace`` along dim 2 at one ``pos`` into a uint8 buffer -> one ``hip_qkv_rope_cache_s8``.
-    Anything else (a result read twice, another position, v through the unscaled chain) stays."""
-    b = rw.bsyms[i]
-    q, k, v = b.output
-    srcs, copies = [], []
-    for j, t in ((ik, k), (iv, v)):
-        bq = rw.bsyms[j]
-        if rw.touched(j) or bq.sym.id not in _KV8_QUANTISE_IDS or _only_tensor_arg(bq) is not t:
-            return
-        outs = bq.output
-        if not isinstance(outs, (tuple, list)) or len(outs) != 2 or not all(isinstance(o, TensorProxy) for o in outs):
-            return
-        srcs.append(outs)
-    (k8, ks), (v8, vs) = srcs
-    pos = None
-    for t in (k8, v8, ks, vs):  # the operator's order: byte caches, then scale caches
-        if rw.uses(t) != 1:
-            return
-        (j,) = rw.consumers(t)
-        c = rw.bsyms[j]
-        if rw.touched(j) or c.sym.name != "index_copy_inplace":
-            return
-        w = operands(c)
-        if w["dim"] != 2 or w["src"] is not t or not isinstance(w["buf"], TensorProxy) or w["buf"].dtype != torch.uint8:
-            return
-        if pos is None:
-            pos = w["index"]
-            if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64:
-                return
-        elif getattr(w["index"], "name", None) != pos.name:
-            return
-        copies.append((j, c, w["buf"]))
-    if len({j for j, _, _ in copies}) != 4:
-        return
-    bufs = [buf for _, _, buf in copies]
-    # placement as for the unscaled write: where the RoPE was when caches and positions exist there, else
-    # at the last cache write, provided nothing in between reads q, a written cache or an earlier write's result
-    ready = max(rw.producer(t, -1) for t in (*bufs, pos))
-    at = i
-    if ready >= i:
-        at = max(j for j, _, _ in copies)
-        if any(i < j < at for j in rw.consumers(q)) or ready >= at:
-            return
-        lo = min(j for j, _, _ in copies)
-        if any(lo < j < at and j not in {x for x, _, _ in copies}
-               for t in (*(c.output for _, c, _ in copies), *bufs) for j in rw.consumers(t)):
-            return
-    rw.replace(at, hip_qkv_rope_cache_s8.bind(*b.args, *bufs, pos, output=(q, *(c.output for _, c, _ in copies))))
-    rw.drop(*({i, ik, iv, *(j for j, _, _ in copies)} - {at}))
+def _cache_sources(rw, t):
+    """How the ``hip_qkv_rope`` result ``t`` (read once) reaches its cache, as ``(kind, the tensors that
+    are copied, the links to drop)``: "plain", ``t`` itself; "e4m3", the uint8 end of
+    ``_e4m3_quantise_chain``; "scaled", the two outputs of ``kv8_quantise_rows``.  None for anything
+    else, and for both e4m3 kinds under LTA_KV8_FUSION=0."""
+    (j,) = rw.consumers(t)
+    b = rw.bsyms[j]
+    if b.sym.name == "index_copy_inplace":
+        return "plain", (t,), ()
+    if _kv8_fusion_off():
+        return None
+    if b.sym.id in _KV8_QUANTISE_IDS:
+        outs = b.output
+        if rw.touched(j) or _only_tensor_arg(b) is not t or not isinstance(outs, (tuple, list)) or len(outs) != 2:
+            return None
+        return ("scaled", tuple(outs), (j,)) if all(isinstance(o, TensorProxy) for o in outs) else None
+    chain = _e4m3_quantise_chain(rw, t)
+    return None if chain is None else ("e4m3", (rw.bsyms[chain[-1]].output,), tuple(chain))
 
 
 def _fuse_kv_cache_writes(trace):
@@ -1076,8 +1038,11 @@ def _fuse_kv_cache_writes(trace):
     converts in the same launch (eight launches fewer per layer).
 
     With the scaled e4m3 cache k and v each pass through ``kv8_quantise_rows`` and their bytes and scale
-    bytes through four ``index_copy_inplace`` at one ``pos``: ``hip_qkv_rope_cache_s8``
-    (``_fuse_scaled_kv_cache_write``)."""
+    bytes through four ``index_copy_inplace``: ``hip_qkv_rope_cache_s8``.
+
+    k and v must reach their caches the same way (``_cache_sources``), and every copied tensor is read
+    once, by an ``index_copy_inplace`` along dim 2 at one int64 ``pos`` into a buffer of its dtype.
+    Anything else (a result read twice, another position, v through another format) stays."""
     rw = Rewrite(trace, ex)
     for i, b in enumerate(rw.bsyms):
         if b.sym is not hip_qkv_rope:
@@ -1085,53 +1050,55 @@ def _fuse_kv_cache_writes(trace):
         q, k, v = b.output
         if rw.uses(k) != 1 or rw.uses(v) != 1:
             continue
-        (ik,), (iv,) = rw.consumers(k), rw.consumers(v)
-        if rw.bsyms[ik].sym.id in _KV8_QUANTISE_IDS or rw.bsyms[iv].sym.id in _KV8_QUANTISE_IDS:
-            if not _kv8_fusion_off():
-                _fuse_scaled_kv_cache_write(rw, i, ik, iv)
+        sk, sv = _cache_sources(rw, k), _cache_sources(rw, v)
+        if sk is None or sv is None or sk[0] != sv[0]:
             continue
-        k_src, v_src, links = k, v, ()
-        if rw.bsyms[ik].sym.name != "index_copy_inplace" and not _kv8_fusion_off():
-            qk, qv = _e4m3_quantise_chain(rw, k), _e4m3_quantise_chain(rw, v)
-            if qk is None or qv is None:
-                continue
-            k_src, v_src, links = rw.bsyms[qk[-1]].output, rw.bsyms[qv[-1]].output, (*qk, *qv)
-            if rw.uses(k_src) != 1 or rw.uses(v_src) != 1:
-                continue
-            (ik,), (iv,) = rw.consumers(k_src), rw.consumers(v_src)
-        ck, cv = rw.bsyms[ik], rw.bsyms[iv]
-        if ck.sym.name != "index_copy_inplace" or cv.sym.name != "index_copy_inplace":
+        srcs = [t for pair in zip(sk[1], sv[1]) for t in pair]  # the operators' order: k, v, then their scales
+        copies, pos = [], None
+        for t in srcs:
+            if rw.uses(t) != 1:
+                break
+            (j,) = rw.consumers(t)
+            c = rw.bsyms[j]
+            if rw.touched(j) or c.sym.name != "index_copy_inplace":
+                break
+            w = operands(c)
+            buf = w["buf"]
+            if w["dim"] != 2 or w["src"] is not t or not isinstance(buf, TensorProxy) or buf.dtype != t.dtype:
+                break
+            if pos is None:
+                pos = w["index"]
+                if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64:
+                    break
+            elif getattr(w["index"], "name", None) != pos.name:
+                break
+            copies.append((j, c.output, buf))
+        if len(copies) != len(srcs):
             continue
-        wk, wv = operands(ck), operands(cv)
-        if wk["dim"] != 2 or wv["dim"] != 2 or wk["src"] is not k_src or wv["src"] is not v_src:
-            continue
-        bk, bv, pos = wk["buf"], wv["buf"], wk["index"]
-        if getattr(pos, "name", None) != getattr(wv["index"], "name", 1):
-            continue
-        if pos.dtype != torch.int64 or bk.dtype != k_src.dtype or bv.dtype != v_src.dtype:
-            continue
+        at_copies, outs, bufs = zip(*copies)
         # the fused op needs the caches and positions: emit it where the RoPE was when they exist
-        # there (LitGPT), else at the later cache write (HF computes the positions after the RoPE),
-        # provided nothing reads q in between
-        ready = max(rw.producer(t, -1) for t in (bk, bv, pos))
+        # there (LitGPT), else at the last cache write (HF computes the positions after the RoPE),
+        # provided nothing in between reads q and, as the earlier writes move later, nothing but the
+        # writes themselves reads a written cache or a write's result
+        ready = max(rw.producer(t, -1) for t in (*bufs, pos))
         at = i
         if ready >= i:
-            at = max(ik, iv)
+            at = max(at_copies)
             if any(i < j < at for j in rw.consumers(q)) or ready >= at:
                 continue
-            # moving the first cache write later: nothing in between may read its result or the
-            # cache it writes
-            lo = min(ik, iv)
-            if any(lo < j < at for t in (ck.output, cv.output, bk, bv) for j in rw.consumers(t)):
+            lo = min(at_copies)
+            if any(lo < j < at and j not in at_copies for t in (*outs, *bufs) for j in rw.consumers(t)):
                 continue
-        rw.replace(at, hip_qkv_rope_cache.bind(*b.args, bk, bv, pos, output=(q, ck.output, cv.output)))
-        rw.drop(*({i, ik, iv, *links} - {at}))
+        op = hip_qkv_rope_cache_s8 if sk[0] == "scaled" else hip_qkv_rope_cache
+        rw.replace(at, op.bind(*b.args, *bufs, pos, output=(q, *outs)))
+        rw.drop(*({i, *sk[2], *sv[2], *at_copies} - {at}))
     return rw.finish(f"hipex: {rw.replaced} KV-cache write pair(s) fused into RoPE")
 
 
 def _e4m3_dequantised(rw, t, dtype):
-    """``(cache, view position, to position)`` when ``t = to(view(cache, float8_e4m3fn), dtype)`` of a
-    uint8 ``cache``, else None."""
+    """``((cache,), view position, (to position, view position))`` when
+    ``t = to(view(cache, float8_e4m3fn), dtype)`` of a uint8 ``cache``, else None: the caches read, where
+    the first link stands, and the links to drop when nothing else reads them, innermost last."""
     j = rw.producer(t)
     if j is None or rw.touched(j):
         return None
@@ -1147,12 +1114,12 @@ def _e4m3_dequantised(rw, t, dtype):
         return None
     if bv.args[1] is not torch.float8_e4m3fn or bv.args[0].dtype != torch.uint8:
         return None
-    return bv.args[0], jv, j
+    return (bv.args[0],), jv, (j, jv)
 
 
 def _kv8_rows_dequantised(rw, t, dtype):
-    """``(cache, scale cache, position)`` when ``t = kv8_dequantise_rows(cache, scales, dtype)`` of uint8
-    operands, else None."""
+    """``((cache, scale cache), position, (position,))`` when ``t = kv8_dequantise_rows(cache, scales, dtype)``
+    of uint8 operands, else None (the shape of ``_e4m3_dequantised``)."""
     j = rw.producer(t)
     if j is None or rw.touched(j):
         return None
@@ -1163,7 +1130,7 @@ def _kv8_rows_dequantised(rw, t, dtype):
     c, s = p["b"], p["scales"]
     if p["dtype"] is not dtype or not all(isinstance(x, TensorProxy) and x.dtype == torch.uint8 for x in (c, s)):
         return None
-    return c, s, j
+    return (c, s), j, (j,)
 
 
 def _fuse_kv8_reads(trace):
@@ -1184,33 +1151,24 @@ def _fuse_kv8_reads(trace):
             continue
         p = operands(b)
         q = p["q"]
-        sk, sv = _kv8_rows_dequantised(rw, p["k"], q.dtype), _kv8_rows_dequantised(rw, p["v"], q.dtype)
-        if sk is not None and sv is not None:
-            (kc, ks, jk), (vc, vs, jv) = sk, sv
-            first = min(jk, jv)
-            if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
-                   for c in (kc, vc, ks, vs) for j in rw.consumers(c)):
-                continue
-            rw.replace(i, hip_decode_attn_kv8s.bind(q, kc, vc, ks, vs, p["mask"], p["causal"], p["scale"],
-                                                    output=b.output))
-            for j, t in ((jk, p["k"]), (jv, p["v"])):
-                if rw.uses(t) == 1:
-                    rw.drop(j)
+        for op, resolve in ((hip_decode_attn_kv8s, _kv8_rows_dequantised), (hip_decode_attn_kv8, _e4m3_dequantised)):
+            rk, rv = resolve(rw, p["k"], q.dtype), resolve(rw, p["v"], q.dtype)
+            if rk is not None and rv is not None:
+                break
+        else:
             continue
-        dk, dv = _e4m3_dequantised(rw, p["k"], q.dtype), _e4m3_dequantised(rw, p["v"], q.dtype)
-        if dk is None or dv is None:
+        caches = [c for pair in zip(rk[0], rv[0]) for c in pair]  # the operators' order: k, v, then their scales
+        # the kernel reads the caches where the attention stands: nothing may write them after the first link
+        first = min(rk[1], rv[1])
+        if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
+               for c in caches for j in rw.consumers(c)):
             continue
-        (kc, *at_k), (vc, *at_v) = dk, dv
-        # the kernel reads the caches where the attention stands: nothing may write them after the views
-        first = min(at_k[0], at_v[0])
-        if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ()) for c in (kc, vc) for j in rw.consumers(c)):
-            continue
-        rw.replace(i, hip_decode_attn_kv8.bind(q, kc, vc, p["mask"], p["causal"], p["scale"], output=b.output))
-        for (jv, jt), t in ((at_k, p["k"]), (at_v, p["v"])):
-            if rw.uses(t) == 1:
-                rw.drop(jt)
-                if rw.uses(rw.bsyms[jv].output) == 1:
-                    rw.drop(jv)
+        rw.replace(i, op.bind(q, *caches, p["mask"], p["causal"], p["scale"], output=b.output))
+        for _, _, links in (rk, rv):
+            for j in links:
+                if rw.uses(rw.bsyms[j].output) != 1:
+                    break
+                rw.drop(j)
     return rw.finish(f"hipex: {rw.replaced} decode attention(s) read their e4m3 KV cache directly")
 
 
@@ -1986,13 +1944,23 @@ def _decode_attn_kv8_meta(q, k8, v8, mask, causal, scale):
     return TensorProxy(like=q)
 
 
-def _decode_attn_kv8_impl(q, k8, v8, mask, causal, scale):
-    from ..ops.attention import decode_attn, decode_attn_kv8, decode_attn_kv8_supported
+def _decode_attn_e4m3_run(q, caches, mask, causal, scale, supported, kernel, dequantise):
+    """Decode attention over e4m3 ``caches`` in operator order (k8, v8, then scale caches): ``kernel``
+    where ``supported`` takes the operands, else (a head dim the e4m3 kernel does not take) the program
+    as the model spells it, ``dequantise(<a cache's operands>, dtype)`` and the 16-bit kernel."""
+    from ..ops.attention import decode_attn
 
-    if decode_attn_kv8_supported(q, k8, v8):
-        return decode_attn_kv8(q, k8, v8, mask, causal, scale)
-    f8 = torch.float8_e4m3fn  # a head dim the e4m3 kernel does not take: the program as the model spells it
-    return decode_attn(q, k8.view(f8).to(q.dtype), v8.view(f8).to(q.dtype), mask, causal, scale)
+    if supported(q, *caches):
+        return kernel(q, *caches, mask, causal, scale)
+    return decode_attn(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), mask, causal, scale)
+
+
+def _decode_attn_kv8_impl(q, k8, v8, mask, causal, scale):
+    from ..ops.attention import decode_attn_kv8, decode_attn_kv8_supported
+    from ..ops.kv8 import e4m3_values
+
+    return _decode_attn_e4m3_run(q, (k8, v8), mask, causal, scale, decode_attn_kv8_supported, decode_attn_kv8,
+                                 e4m3_values)
 
 
 hip_decode_attn_kv8 = ex.register_operator("hip_decode_attn_kv8", meta=_decode_attn_kv8_meta, fn=_decode_attn_kv8_impl)
@@ -2003,14 +1971,11 @@ def _decode_attn_kv8s_meta(q, k8, v8, k_scale, v_scale, mask, causal, scale):
 
 
 def _decode_attn_kv8s_impl(q, k8, v8, k_scale, v_scale, mask, causal, scale):
-    from ..ops.attention import decode_attn, decode_attn_kv8s, decode_attn_kv8s_supported
+    from ..ops.attention import decode_attn_kv8s, decode_attn_kv8s_supported
     from ..ops.kv8 import dequantise_rows
 
-    if decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale):
-        return decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask, causal, scale)
-    # a head dim the e4m3 kernel does not take: the program as the model spells it
-    return decode_attn(q, dequantise_rows(k8, k_scale, q.dtype), dequantise_rows(v8, v_scale, q.dtype), mask, causal,
-                       scale)
+    return _decode_attn_e4m3_run(q, (k8, v8, k_scale, v_scale), mask, causal, scale, decode_attn_kv8s_supported,
+                                 decode_attn_kv8s, dequantise_rows)
 
 
 hip_decode_attn_kv8s = ex.register_operator("hip_decode_attn_kv8s", meta=_decode_attn_kv8s_meta,

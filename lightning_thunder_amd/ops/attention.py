@@ -377,17 +377,14 @@ def attn_bwd_rope(do, q, k, v, o, lse, causal: bool, scale, cos, sin, n_head: in
 import ctypes  # noqa: E402
 
 from ._lib import c_int64  # noqa: E402
+from .kv8 import scale_caches_of  # noqa: E402
 
-register_signature("lta_decode_attn", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float,
-                                       c_int, c_void_p])
+# the decode entries: pointers q, k, v, <scale caches>, mask, o, ws_acc, ws_ml
+for _entry, _scale_ptrs in (("lta_decode_attn", 0), ("lta_decode_attn_kv8", 0), ("lta_decode_attn_kv8s", 2)):
+    register_signature(_entry, [c_int, *[c_void_p] * (7 + _scale_ptrs), *[c_int] * 6, c_void_p, c_int, c_int, c_int,
+                                c_float, c_int, c_void_p])
 
 DECODE_MAX_QUERIES = 16
-
-
-def _aligned_rows(t: torch.Tensor) -> torch.Tensor:
-    """Head dim contiguous and every row start 16-byte aligned (the kernel uses 16-byte loads)."""
-    return _rows_in_place(t)
 
 
 def decode_launch_shape(rows: int, S: int):
@@ -436,13 +433,8 @@ def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None,
 
 def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = None):
     """q [B, Hq, T, D] (T <= 16), k/v [B, Hkv, S, D], mask bool broadcastable to [B, Hq, T, S] -> [B, Hq, T, D]."""
-    q, k, v = _aligned_rows(q), _aligned_rows(k), _aligned_rows(v)
+    q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
     return _decode_launch("lta_decode_attn", q, k, v, mask, causal, scale)
-
-
-register_signature("lta_decode_attn_kv8", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
-                                           c_float, c_int, c_void_p])
 
 
 def decode_attn_kv8_supported(q, k8, v8) -> bool:
@@ -467,26 +459,14 @@ def decode_attn_kv8(q, k8, v8, mask=None, causal: bool = False, scale: float | N
     if not decode_attn_kv8_supported(q, k8, v8):
         raise ValueError(f"decode_attn_kv8: unsupported operands q {q.dtype} {tuple(q.shape)}, "
                          f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}")
-    q, k8, v8 = _aligned_rows(q), _rows8_in_place(k8), _rows8_in_place(v8)
+    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
     return _decode_launch("lta_decode_attn_kv8", q, k8, v8, mask, causal, scale)
-
-
-register_signature("lta_decode_attn_kv8s", [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                            c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int,
-                                            c_int, c_int, c_float, c_int, c_void_p])
 
 
 def decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale) -> bool:
     """What the scaled-e4m3 decode kernel takes: the operands of ``decode_attn_kv8`` plus uint8 scale
     caches [B, Hkv, S, 1] on the same device (any strides: a lane loads single bytes)."""
-    if not decode_attn_kv8_supported(q, k8, v8):
-        return False
-    for s in (k_scale, v_scale):
-        if s is None or s.dtype != torch.uint8 or s.device != k8.device or s.dim() != 4:
-            return False
-        if tuple(s.shape) != (*k8.shape[:3], 1):
-            return False
-    return True
+    return decode_attn_kv8_supported(q, k8, v8) and scale_caches_of((k_scale, v_scale), (k8, v8))
 
 
 def decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask=None, causal: bool = False, scale: float | None = None):
@@ -499,5 +479,5 @@ def decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask=None, causal: bool = Fals
                          f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, scales "
                          f"{None if k_scale is None else (k_scale.dtype, tuple(k_scale.shape))} / "
                          f"{None if v_scale is None else (v_scale.dtype, tuple(v_scale.shape))}")
-    q, k8, v8 = _aligned_rows(q), _rows8_in_place(k8), _rows8_in_place(v8)
+    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
     return _decode_launch("lta_decode_attn_kv8s", q, k8, v8, mask, causal, scale, scales=(k_scale, v_scale))

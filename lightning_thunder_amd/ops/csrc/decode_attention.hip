@@ -161,23 +161,18 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     m = m_new;
     if (valid) {
       const KV* vrow = vbase + (int64_t)j * vss;
-      [[maybe_unused]] const float pv = p * __uint_as_float(vb << 23);
+      const float pv = KS ? p * __uint_as_float(vb << 23) : p;
 #pragma unroll
       for (int d = 0; d < D; d += NV) {
-        if constexpr (KS) {
+        if constexpr (kE4M3) {
           float x[NV];
           load16_e4m3(vrow + d, x);
 #pragma unroll
           for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(pv, x[e], acc[d + e] * corr);
-        } else if constexpr (kE4M3) {
-          float x[NV];
-          load16_e4m3(vrow + d, x);
-#pragma unroll
-          for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(p, x[e], acc[d + e] * corr);
         } else {
           Vec16<T> x = load16(vrow + d);
 #pragma unroll
-          for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(p, to_f32(x.v[e]), acc[d + e] * corr);
+          for (int e = 0; e < NV; ++e) acc[d + e] = fmaf(pv, to_f32(x.v[e]), acc[d + e] * corr);
         }
       }
     } else {
@@ -293,6 +288,28 @@ int launch(const void* q, const void* k, const void* v, const void* mask, void* 
   return (int)hipGetLastError();
 }
 
+// `launch` for q / o of `dtype` and head dim D; KV = void: the cache holds q's type.  `a`: launch's arguments.
+template <typename KV, bool KS = false, typename... A>
+int dispatch(int dtype, int D, A... a) {
+  using B16 = __hip_bfloat16;
+  constexpr bool kSame = std::is_void_v<KV>;
+  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS>(a...);
+  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS>(a...);
+  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS>(a...);
+  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS>(a...);
+  return (int)hipErrorInvalidValue;
+}
+
+// what every entry requires of its sizes
+bool sizes_ok(int Hq, int Hkv, int chunk, int nsplit) { return Hkv > 0 && Hq % Hkv == 0 && chunk > 0 && nsplit > 0; }
+
+// an e4m3 cache is read with 16-byte loads: k / v strides (strides[3..8], bytes) and bases are multiples of 16
+bool e4m3_cache_ok(const void* k, const void* v, const int64_t* strides) {
+  for (int i = 3; i < 9; ++i)
+    if (strides[i] % 16) return false;
+  return (((uintptr_t)k | (uintptr_t)v) % 16) == 0;
+}
+
 }  // namespace
 }  // namespace lta
 
@@ -302,16 +319,9 @@ LTA_EXPORT int lta_decode_attn(int dtype, const void* q, const void* k, const vo
                                const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit,
                                void* stream) {
   using namespace lta;
-  hipStream_t s = (hipStream_t)stream;
-  if (Hkv <= 0 || Hq % Hkv != 0 || chunk <= 0 || nsplit <= 0) return (int)hipErrorInvalidValue;
-  if (dtype == kBF16) {
-    if (D == 64) return launch<__hip_bfloat16, __hip_bfloat16, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-    if (D == 128) return launch<__hip_bfloat16, __hip_bfloat16, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-  } else if (dtype == kF16) {
-    if (D == 64) return launch<__half, __half, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-    if (D == 128) return launch<__half, __half, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-  }
-  return (int)hipErrorInvalidValue;
+  if (!sizes_ok(Hq, Hkv, chunk, nsplit)) return (int)hipErrorInvalidValue;
+  return dispatch<void>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal,
+                        scale, wsplit, (hipStream_t)stream);
 }
 
 // The same launch over an unscaled OCP e4m3 cache: k / v are uint8 [B, Hkv, S, D] (strides in elements
@@ -321,19 +331,9 @@ LTA_EXPORT int lta_decode_attn_kv8(int dtype, const void* q, const void* k, cons
                                    const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit,
                                    void* stream) {
   using namespace lta;
-  hipStream_t s = (hipStream_t)stream;
-  if (Hkv <= 0 || Hq % Hkv != 0 || chunk <= 0 || nsplit <= 0) return (int)hipErrorInvalidValue;
-  for (int i = 3; i < 9; ++i)
-    if (strides[i] % 16) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)k | (uintptr_t)v) % 16) return (int)hipErrorInvalidValue;
-  if (dtype == kBF16) {
-    if (D == 64) return launch<__hip_bfloat16, uint8_t, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-    if (D == 128) return launch<__hip_bfloat16, uint8_t, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-  } else if (dtype == kF16) {
-    if (D == 64) return launch<__half, uint8_t, 64>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-    if (D == 128) return launch<__half, uint8_t, 128>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s);
-  }
-  return (int)hipErrorInvalidValue;
+  if (!sizes_ok(Hq, Hkv, chunk, nsplit) || !e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
+  return dispatch<uint8_t>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal,
+                           scale, wsplit, (hipStream_t)stream);
 }
 
 // The same launch over the scaled e4m3 cache of ops/kv8.py: k / v as for lta_decode_attn_kv8, k_scale / v_scale
@@ -343,20 +343,10 @@ LTA_EXPORT int lta_decode_attn_kv8s(int dtype, const void* q, const void* k, con
                                     int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int chunk, int nsplit,
                                     int causal, float scale, int wsplit, void* stream) {
   using namespace lta;
-  hipStream_t s = (hipStream_t)stream;
-  if (Hkv <= 0 || Hq % Hkv != 0 || chunk <= 0 || nsplit <= 0) return (int)hipErrorInvalidValue;
+  if (!sizes_ok(Hq, Hkv, chunk, nsplit) || !e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
   if (k_scale == nullptr || v_scale == nullptr) return (int)hipErrorInvalidValue;
-  for (int i = 3; i < 9; ++i)
-    if (strides[i] % 16) return (int)hipErrorInvalidValue;
-  if (((uintptr_t)k | (uintptr_t)v) % 16) return (int)hipErrorInvalidValue;
   const KVScales sc{(const uint8_t*)k_scale, (const uint8_t*)v_scale, strides[13], strides[14], strides[15],
                     strides[16], strides[17], strides[18]};
-  if (dtype == kBF16) {
-    if (D == 64) return launch<__hip_bfloat16, uint8_t, 64, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
-    if (D == 128) return launch<__hip_bfloat16, uint8_t, 128, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
-  } else if (dtype == kF16) {
-    if (D == 64) return launch<__half, uint8_t, 64, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
-    if (D == 128) return launch<__half, uint8_t, 128, true>(q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal, scale, wsplit, s, sc);
-  }
-  return (int)hipErrorInvalidValue;
+  return dispatch<uint8_t, true>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit,
+                                 causal, scale, wsplit, (hipStream_t)stream, sc);
 }

@@ -366,27 +366,31 @@ LTA_EXPORT int lta_qkv_rope_cache_fwd(int dtype, int cdtype, const void* qkv, co
 // As lta_qkv_rope_cache_fwd with uint8 caches holding unscaled OCP e4m3: k (rotated) and v are rounded
 // to the activation dtype, saturated to +-448 and converted (round to nearest even), 8 bytes per store.
 // Row-kernel shapes only (rope_n == hs, hs / 16 a power of two, 16-bit activations): -2 otherwise.
-LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
-                                          void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
-                                          int Tn, int nh, int ng, int hs, int rope_n, hipStream_t stream) {
+// KS: the scaled cache, its scale bytes through `sd`.
+template <bool KS>
+static int qkv_rope_e4m3_launch(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_, void* q,
+                                void* kc, void* vc, const void* pos, const int64_t* strides, int B, int Tn, int nh,
+                                int ng, int hs, int rope_n, hipStream_t stream,
+                                std::conditional_t<KS, ScaleDst, NoScale> sd) {
   if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
   if (((uintptr_t)kc | (uintptr_t)vc) % 8) return -2;
   const int sh = row_pair_shift(dtype, hs, rope_n);
   if (sh < 0 || dtype == kF32) return -2;
   const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
-  auto launch = [&](auto t, auto c) {
-    using T = decltype(t);
-    using C = decltype(c);
-    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t>), dim3(B * Tn), dim3(256), 0, stream, (const T*)qkv,
-                       (const T*)nullptr, (const T*)nullptr, (const C*)cos_, (const C*)sin_, (T*)q, (uint8_t*)kc,
-                       (uint8_t*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs, sh, NoScale{});
-    return (int)hipGetLastError();
-  };
-  if (dtype == kBF16 && cdtype == kF32) return launch(__hip_bfloat16{}, float{});
-  if (dtype == kBF16 && cdtype == kBF16) return launch(__hip_bfloat16{}, __hip_bfloat16{});
-  if (dtype == kF16 && cdtype == kF32) return launch(__half{}, float{});
-  if (dtype == kF16 && cdtype == kF16) return launch(__half{}, __half{});
-  return -1;
+  LTA_DISPATCH_TC(dtype, cdtype,
+                  if constexpr (sizeof(T) == 2)  // fp32 activations were refused above: no such kernel is built
+                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, KS>), dim3(B * Tn), dim3(256), 0,
+                                       stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
+                                       (const C*)sin_, (T*)q, (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn,
+                                       nh, ng, hs, sh, sd));
+  return (int)hipGetLastError();
+}
+
+LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
+                                          void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
+                                          int Tn, int nh, int ng, int hs, int rope_n, hipStream_t stream) {
+  return qkv_rope_e4m3_launch<false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs, rope_n,
+                                     stream, NoScale{});
 }
 
 // As lta_qkv_rope_cache_fwd_kv8 for the scaled e4m3 cache of ops/kv8.py: every k / v head row is stored as
@@ -396,25 +400,10 @@ LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s(int dtype, int cdtype, const void* qk
                                            void* q, void* kc, void* vc, void* ksc, void* vsc, const void* pos,
                                            const int64_t* strides, int B, int Tn, int nh, int ng, int hs, int rope_n,
                                            hipStream_t stream) {
-  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
-  if (((uintptr_t)kc | (uintptr_t)vc) % 8) return -2;
-  const int sh = row_pair_shift(dtype, hs, rope_n);
-  if (sh < 0 || sh > 6 || dtype == kF32) return -2;
-  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  if (row_pair_shift(dtype, hs, rope_n) > 6) return -2;
   const ScaleDst sd{(uint8_t*)ksc, (uint8_t*)vsc, strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
-  auto launch = [&](auto t, auto c) {
-    using T = decltype(t);
-    using C = decltype(c);
-    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, true>), dim3(B * Tn), dim3(256), 0, stream,
-                       (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_, (const C*)sin_, (T*)q,
-                       (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs, sh, sd);
-    return (int)hipGetLastError();
-  };
-  if (dtype == kBF16 && cdtype == kF32) return launch(__hip_bfloat16{}, float{});
-  if (dtype == kBF16 && cdtype == kBF16) return launch(__hip_bfloat16{}, __hip_bfloat16{});
-  if (dtype == kF16 && cdtype == kF32) return launch(__half{}, float{});
-  if (dtype == kF16 && cdtype == kF16) return launch(__half{}, __half{});
-  return -1;
+  return qkv_rope_e4m3_launch<true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs, rope_n,
+                                    stream, sd);
 }
 
 LTA_EXPORT int lta_qkv_rope_bwd(int dtype, int cdtype, const void* dq, const void* dk, const void* dv, const void* cos_,

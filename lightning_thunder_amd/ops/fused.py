@@ -6,17 +6,14 @@ import ctypes
 import torch
 
 from ._lib import require, dcode, ptr, stream_ptr, check, register_signature, c_int, c_int64, c_void_p, c_float
+from .kv8 import scale_caches_of
 
 register_signature("lta_qkv_rope_fwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
-register_signature("lta_qkv_rope_cache_fwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
-register_signature("lta_qkv_rope_cache_fwd_kv8", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                  c_void_p])
-register_signature("lta_qkv_rope_cache_fwd_kv8s", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                                   c_int, c_int, c_int, c_void_p])
+# the cache-writing entries: pointers qkv, cos, sin, q, kc, vc, <scale caches>, pos, strides
+for _entry, _scale_ptrs in (("lta_qkv_rope_cache_fwd", 0), ("lta_qkv_rope_cache_fwd_kv8", 0),
+                            ("lta_qkv_rope_cache_fwd_kv8s", 2)):
+    register_signature(_entry, [c_int, c_int, *[c_void_p] * (8 + _scale_ptrs), *[c_int] * 6, c_void_p])
 register_signature("lta_qkv_rope_bwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
 register_signature("lta_swiglu_fwd", [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -66,19 +63,15 @@ def qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups: int, head_size: i
     uint8 caches (unscaled e4m3, 8-byte aligned rows) only at the row kernel's shapes: full rotation
     (``rope_n``, taken as ``head_size`` when not given) and ``head_size / 16`` a power of two."""
     B, T, _ = qkv.shape
-    if kc.dtype == torch.uint8 and vc.dtype == torch.uint8:
-        if not _row_kernel_shape(qkv.dtype, head_size, head_size if rope_n is None else rope_n):
-            return False
-        for c in (kc, vc):
-            if c.dim() != 4 or tuple(c.shape[:2]) != (B, n_query_groups) or c.shape[3] != head_size:
-                return False
-            if c.stride(3) != 1 or any(st % 8 for st in c.stride()[:3]) or c.data_ptr() % 8:
-                return False
-        return pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == T and pos.is_contiguous()
+    kv8 = kc.dtype == torch.uint8 and vc.dtype == torch.uint8
+    if kv8 and not _row_kernel_shape(qkv.dtype, head_size, head_size if rope_n is None else rope_n):
+        return False
     for c in (kc, vc):
-        if c.dtype != qkv.dtype or c.dim() != 4 or tuple(c.shape[:2]) != (B, n_query_groups) or c.shape[3] != head_size:
+        if c.dtype != (torch.uint8 if kv8 else qkv.dtype) or c.dim() != 4:
             return False
-        if c.stride(3) != 1 or any(st % 8 for st in c.stride()[:3]) or c.data_ptr() % 16:
+        if tuple(c.shape[:2]) != (B, n_query_groups) or c.shape[3] != head_size:
+            return False
+        if c.stride(3) != 1 or any(st % 8 for st in c.stride()[:3]) or c.data_ptr() % (8 if kv8 else 16):
             return False
     return pos.dtype == torch.int64 and pos.dim() == 1 and pos.numel() == T and pos.is_contiguous()
 
@@ -89,29 +82,24 @@ def qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_
     within one wave (``head_size <= 1024``), and uint8 scale caches [B, ng, S, 1] over the same rows."""
     if kc.dtype != torch.uint8 or vc.dtype != torch.uint8 or head_size > 1024:
         return False
-    if not qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size, rope_n):
-        return False
-    for s, c in ((k_scale, kc), (v_scale, vc)):
-        if s is None or s.dtype != torch.uint8 or s.device != c.device or s.dim() != 4:
-            return False
-        if tuple(s.shape) != (*c.shape[:3], 1):
-            return False
-    return True
+    return (qkv_rope_cache_supported(qkv, kc, vc, pos, n_query_groups, head_size, rope_n)
+            and scale_caches_of((k_scale, v_scale), (kc, vc)))
 
 
 def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kc, vc, pos,
                        k_scale=None, v_scale=None):
     """qkv split + RoPE with k / v written in place into the static caches ``kc`` / ``vc`` at rows
     ``pos`` (the decode step's ``index_copy_`` fused into the same launch).  Returns (q, kc, vc).
-    uint8 caches receive the rows as unscaled saturating e4m3: bit for bit
-    ``k.clamp(-448, 448).to(float8_e4m3fn).view(uint8)`` of ``qkv_rope_fwd``'s k (and v).
+    uint8 caches receive the rows as unscaled saturating e4m3: bit for bit ``ops/kv8.py``'s ``e4m3_bytes``
+    of ``qkv_rope_fwd``'s k (and v).
     With ``k_scale`` / ``v_scale`` (uint8 [B, ng, S, 1]) the caches are the scaled ones of ``ops/kv8.py``:
     bytes and scale bytes equal ``quantise_rows`` of ``qkv_rope_fwd``'s k (and v) bit for bit, and the
     result is (q, kc, vc, k_scale, v_scale)."""
     if (k_scale is None) != (v_scale is None):
         raise ValueError("qkv_rope_cache_fwd: k_scale and v_scale come together")
-    if k_scale is not None and not qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_groups,
-                                                                   head_size, rope_n):
+    scales = () if k_scale is None else (k_scale, v_scale)
+    if scales and not qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_groups, head_size,
+                                                      rope_n):
         raise ValueError("qkv_rope_cache_fwd: operands the scaled e4m3 write does not take "
                          "(see qkv_rope_cache_scaled_supported)")
     lib = require()
@@ -124,19 +112,13 @@ def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_siz
     if cos.dtype not in (torch.float32, qkv.dtype):
         cos, sin = cos.float(), sin.float()
     q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
-    if k_scale is not None:
-        st = (ctypes.c_int64 * 12)(*kc.stride()[:3], *vc.stride()[:3], *k_scale.stride()[:3], *v_scale.stride()[:3])
-        rc = lib.lta_qkv_rope_cache_fwd_kv8s(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), ptr(kc),
-                                             ptr(vc), ptr(k_scale), ptr(v_scale), ptr(pos), st, B, T, n_head,
-                                             n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
-        check(rc, "lta_qkv_rope_cache_fwd_kv8s")
-        return q, kc, vc, k_scale, v_scale
-    st = (ctypes.c_int64 * 6)(*kc.stride()[:3], *vc.stride()[:3])
-    entry ="lta_qkv_rope_cache_fwd_kv8" if kc.dtype == torch.uint8 else "lta_qkv_rope_cache_fwd"
-    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), ptr(kc), ptr(vc),
-                             ptr(pos), st, B, T, n_head, n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
+    caches = (kc, vc, *scales)
+    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches for s in c.stride()[:3]))
+    entry = "lta_qkv_rope_cache_fwd" + ("_kv8s" if scales else "_kv8" if kc.dtype == torch.uint8 else "")
+    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), *map(ptr, caches), ptr(pos),
+                             st, B, T, n_head, n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
     check(rc, entry)
-    return q, kc, vc
+    return (q, *caches)
 
 
 def qkv_rope_bwd(dq, dk, dv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int):

@@ -1,7 +1,8 @@
-"""The scaled e4m3 KV cache's number format: one power-of-two scale per row, in plain torch.
+"""The two e4m3 KV cache formats in plain torch: unscaled, and one power-of-two scale per row.
 
-``quantise_rows`` / ``dequantise_rows`` are the definition; the kernels (``csrc/rope.hip`` row kernel,
-``csrc/decode_attention.hip``) equal them bit for bit.  A row ``x[..., :]`` is stored as ``D`` bytes of OCP
+``e4m3_bytes`` / ``e4m3_values`` (unscaled) and ``quantise_rows`` / ``dequantise_rows`` (scaled) are the
+definition; the kernels (``csrc/rope.hip`` row kernel, ``csrc/decode_attention.hip``) equal them bit for
+bit.  A scaled row ``x[..., :]`` is stored as ``D`` bytes of OCP
 e4m3 (``float8_e4m3fn``) of ``x * 2^-e`` plus one byte ``e + 127`` (E8M0 style), where ``e`` is the
 smallest exponent in [-15, 7] with ``amax * 2^-e <= 448``.  Multiplying by a power of two is exact, so the
 only rounding is the e4m3 conversion, whose error is relative: the same 2^-4 at every magnitude from
@@ -19,9 +20,27 @@ from __future__ import annotations
 
 import torch
 
+E4M3_MAX = 448.0
 E_MIN, E_MAX = -15, 7
 SCALE_BIAS = 127
 _F8 = torch.float8_e4m3fn
+
+
+def e4m3_bytes(x: torch.Tensor) -> torch.Tensor:
+    """The stored form of an unscaled e4m3 value: saturate, round to nearest even, as uint8."""
+    return x.clamp(-E4M3_MAX, E4M3_MAX).to(_F8).view(torch.uint8)
+
+
+def e4m3_values(b: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The values of e4m3 bytes in ``dtype`` (exact for bf16 / fp16 / fp32)."""
+    return b.view(_F8).to(dtype)
+
+
+def scale_caches_of(scales, caches) -> bool:
+    """Every ``scales[i]`` holds the scale bytes of the byte cache ``caches[i]`` [B, H, S, D]: uint8
+    [B, H, S, 1] on its device (any strides)."""
+    return all(s is not None and s.dtype == torch.uint8 and s.device == c.device and s.dim() == 4
+               and tuple(s.shape) == (*c.shape[:3], 1) for s, c in zip(scales, caches))
 
 
 def pow2(n: torch.Tensor) -> torch.Tensor:
@@ -41,13 +60,12 @@ def row_exponent(x: torch.Tensor) -> torch.Tensor:
 def quantise_rows(x: torch.Tensor):
     """``x [..., D]`` float -> ``(bytes uint8 [..., D], scales uint8 [..., 1])``."""
     e = row_exponent(x)
-    b = (x.float() * pow2(-e)).clamp(-448.0, 448.0).to(_F8).view(torch.uint8)
-    return b, (e + SCALE_BIAS).to(torch.uint8)
+    return e4m3_bytes(x.float() * pow2(-e)), (e + SCALE_BIAS).to(torch.uint8)
 
 
 def dequantise_rows(b: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """``bytes * 2^(scales - 127)`` in ``dtype``; exact for bf16 / fp16 / fp32 with scales in [112, 134]."""
-    return b.view(_F8).to(dtype) * pow2(scales.to(torch.int32) - SCALE_BIAS).to(dtype)
+    return e4m3_values(b, dtype) * pow2(scales.to(torch.int32) - SCALE_BIAS).to(dtype)
 
 
 @torch.library.custom_op("lta::kv8_quantise_rows", mutates_args=())

@@ -22,8 +22,7 @@ from __future__ import annotations
 import torch
 
 from ..core.transform_common import Transform
-
-E4M3_MAX = 448.0
+from ..ops.kv8 import E4M3_MAX, e4m3_bytes
 
 
 def quantize_weight_e4m3(w: torch.Tensor):
@@ -31,7 +30,7 @@ def quantize_weight_e4m3(w: torch.Tensor):
     wf = w.detach().float()
     amax = wf.abs().amax().clamp_min(1e-12)
     scale = (E4M3_MAX / amax).to(torch.float32)
-    q = (wf * scale).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    q = e4m3_bytes(wf * scale)
     return q.contiguous(), scale.reshape(())
 
 
@@ -93,7 +92,7 @@ def quantize_experts_e4m3(w: torch.Tensor):
     wf = w.detach().float()
     amax = wf.abs().amax(dim=(1, 2)).clamp_min(1e-12)
     scale = (E4M3_MAX / amax).to(torch.float32)
-    q = (wf * scale[:, None, None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    q = e4m3_bytes(wf * scale[:, None, None])
     return q.contiguous(), scale.contiguous()
 
 

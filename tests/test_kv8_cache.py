@@ -154,7 +154,13 @@ def _write_program(case=None):
         extra.append(s)
     if case == "v_bytes_returned":
         extra.append(links_v[2])
+    if case == "late_q_read":
+        extra.append(p(lt.neg, q, out=p.t("s", 1, 4, 1, 64)))
+    if case is not None and case.startswith("late"):  # the positions are computed after the RoPE
+        p(lt.silu, p.t("p0", 1, dtype=I64), out=pos)
     p(index_copy_inplace, kc, 2, pos, links_k[2], out=kc2)
+    if case == "late_cache_read":  # between the two writes, which would both move to the later one
+        extra.append(p(lt.neg, vc, out=p.t("s", 1, 4, 32, 64, dtype=U8)))
     p(index_copy_inplace, vc, 2, pos2 if case == "other_positions" else pos, links_v[2], out=vc2)
     return p.run(q, kc2, vc2, *extra)
 
@@ -184,8 +190,13 @@ def test_kv8_writes_fused_under_the_torch_executor_names():
     assert p.run(q, kc2, vc2) == ([_ROPE_CACHE], _KV)
 
 
+def test_kv8_writes_emitted_at_the_later_write():
+    assert _write_program("late") == (["pos = silu(p0)", _ROPE_CACHE], _KV)
+
+
 @pytest.mark.parametrize("case", ["bounds", "upper_bound", "no_clamp", "e5m2", "clamp_read_twice", "cast_read_twice",
-                                  "bytes_read_twice", "v_bytes_returned", "other_positions", "bf16_cache"])
+                                  "bytes_read_twice", "v_bytes_returned", "other_positions", "bf16_cache",
+                                  "late_q_read", "late_cache_read"])
 def test_kv8_writes_refused(case):
     unchanged(_write_program(case))
 

@@ -203,8 +203,11 @@ def _write_program(case=None):
     k8, v8 = p.ts("k8 v8", 1, 4, 1, 64, dtype=U8)
     ks, vs = p.ts("ks vs", 1, 4, 1, 1, dtype=U8)
     p(hipex.hip_qkv_rope, qkv, cos, sin, 4, 4, 64, 64, out=(q, k, v))
-    p(QUANTISE, k, out=(k8, ks))
     extra = []
+    if case == "mixed_reverse":  # k through the unscaled cache's chain
+        _, _, k8 = _quantise(p, k, "k")
+    else:
+        p(QUANTISE, k, out=(k8, ks))
     if case == "mixed":  # v through the unscaled cache's chain
         _, _, v8 = _quantise(p, v, "v")
     else:
@@ -216,8 +219,17 @@ def _write_program(case=None):
             extra.append(s)
     if case == "scale_returned":
         extra.append(ks)
+    if case == "late_q_read":
+        extra.append(p(lt.neg, q, out=p.t("s", 1, 4, 1, 64)))
+    if case is not None and case.startswith("late"):  # the positions are computed after the RoPE
+        p(lt.silu, p.t("p0", 1, dtype=I64), out=pos)
     p(index_copy_inplace, kc, 2, pos, k8, out=kc2)
+    if case == "late_cache_read":  # between the first and the last write, which would all move to the last
+        extra.append(p(lt.neg, vsc, out=p.t("s", 1, 4, 32, 1, dtype=U8)))
     p(index_copy_inplace, vc, 2, pos, v8, out=vc2)
+    if case == "mixed_reverse":
+        p(index_copy_inplace, vsc, 2, pos, vs, out=vsc2)
+        return p.run(q, kc2, vc2, vsc2, *extra)
     p(index_copy_inplace, ksc, 2, pos2 if case == "scale_at_other_positions" else pos, ks, out=ksc2)
     if case != "mixed":
         p(index_copy_inplace, vsc, 3 if case == "other_dim" else 2, pos, vs, out=vsc2)
@@ -229,8 +241,12 @@ def test_scaled_writes_fused_into_the_rope():
     assert _write_program() == ([_ROPE_S8], _KV)
 
 
+def test_scaled_writes_emitted_at_the_last_write():
+    assert _write_program("late") == (["pos = silu(p0)", _ROPE_S8], _KV)
+
+
 @pytest.mark.parametrize("case", ["scale_at_other_positions", "bytes_read_twice", "scale_read_twice", "scale_returned",
-                                  "mixed", "other_dim"])
+                                  "mixed", "mixed_reverse", "other_dim", "late_q_read", "late_cache_read"])
 def test_scaled_writes_refused(case):
     unchanged(_write_program(case))
 
