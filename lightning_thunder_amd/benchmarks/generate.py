@@ -17,6 +17,10 @@ prompt; no checkpoints offline): greedy decoding of ``--new-tokens`` tokens afte
   ``model.generate(cache_implementation="static")``, eager or through
   ``compile(recipe="hf-transformers"[, plugins="reduce-overhead"])``.
 
+``--prompt-lengths a,b,c,...`` with a matching ``--batch-size`` (LitGPT modes only) generates for a ragged batch:
+the prompt is right-padded to the longest length and decoding runs at per-sequence positions
+(``generate(..., prompt_lengths=...)``).
+
 Prints one JSON line per mode: mean latency (ms) of ``--iters`` full generations after
 ``--warmup`` untimed ones.
 """
@@ -32,7 +36,7 @@ import torch
 from . import KV_CACHE_FORMATS
 
 
-def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model"):
+def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model", batch_size: int = 1):
     from ..models.litgpt import GPT, Config, init_weights
 
     kw = {} if n_layer is None else {"n_layer": n_layer}
@@ -44,7 +48,7 @@ def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: 
     init_weights(model)
     model.requires_grad_(False)
     model.eval()
-    model.set_kv_cache(1, max_seq, device=device, **KV_CACHE_FORMATS[kv_cache_dtype])
+    model.set_kv_cache(batch_size, max_seq, device=device, **KV_CACHE_FORMATS[kv_cache_dtype])
     return model, cfg
 
 
@@ -88,8 +92,12 @@ def run(mode: str, args) -> dict:
         def once():
             return gm.generate(prompt, **kw)
     else:
-        model, cfg = _build(args.model, args.prompt_len + args.new_tokens + 8, device, args.n_layer, args.kv_cache_dtype)
-        prompt = torch.randint(0, cfg.vocab_size, (1, args.prompt_len), device=device)
+        model, cfg = _build(args.model, args.prompt_len + args.new_tokens + 8, device, args.n_layer, args.kv_cache_dtype,
+                            args.batch_size)
+        prompt = torch.randint(0, cfg.vocab_size, (args.batch_size, args.prompt_len), device=device)
+        lengths = None
+        if args.prompt_lengths is not None:
+            lengths = torch.tensor(args.prompt_lengths, dtype=torch.int64, device=device)
         if mode == "eager":
             fwd = model
         elif mode == "thunder":
@@ -109,7 +117,7 @@ def run(mode: str, args) -> dict:
             if sampling:  # every timed generation draws the same tokens
                 torch.manual_seed(args.seed)
             return generate(model, prompt, args.new_tokens, forward=fwd, temperature=args.temperature,
-                            top_k=args.top_k, top_p=args.top_p)
+                            top_k=args.top_k, top_p=args.top_p, prompt_lengths=lengths)
 
     t0 = time.perf_counter()
     out = once()
@@ -131,7 +139,8 @@ def run(mode: str, args) -> dict:
         "model_impl": "transformers.LlamaForCausalLM" if mode.startswith("hf_") else "lightning_thunder_amd litgpt GPT",
         "mode": mode, "value": round(ms, 2), "unit": "ms", "higher_is_better": False,
         "ms_per_token": round(ms / args.new_tokens, 3), "first_call_s": round(first, 2),
-        "prompt_len": args.prompt_len, "new_tokens": args.new_tokens,
+        "prompt_len": args.prompt_len, "new_tokens": args.new_tokens, "batch_size": args.batch_size,
+        "prompt_lengths": args.prompt_lengths,
         "kv_cache_dtype": "model" if mode.startswith("hf_") else args.kv_cache_dtype,
         "dtype": "mxfp4 weights, bf16 activations" if mode.endswith("mxfp4") else "bf16",
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
@@ -139,7 +148,8 @@ def run(mode: str, args) -> dict:
     }
     if sampling:
         res.update(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
-    res["tokens"] = out[0, -args.new_tokens:].tolist()
+    first_new = args.prompt_lengths[0] if args.prompt_lengths and not mode.startswith("hf_") else out.shape[1] - args.new_tokens
+    res["tokens"] = out[0, first_new:first_new + args.new_tokens].tolist()
     return res
 
 
@@ -168,7 +178,23 @@ def main(argv=None):
                    help="LitGPT modes: 'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes), "
                         "'fp8-row' as e4m3 with one power-of-two scale byte per (token, kv head) row")
     p.add_argument("--seed", type=int, default=0, help="torch.manual_seed before every sampled generation")
+    p.add_argument("--batch-size", type=int, default=1, help="LitGPT modes: sequences per generation")
+    p.add_argument("--prompt-lengths", default=None,
+                   help="LitGPT modes: a,b,c,... one prompt length per sequence (a ragged batch, right-padded to the "
+                        "longest, which replaces --prompt-len); --batch-size must match")
     args = p.parse_args(argv)
+    if args.prompt_lengths is not None:
+        try:
+            args.prompt_lengths = [int(x) for x in args.prompt_lengths.split(",")]
+        except ValueError:
+            p.error("--prompt-lengths takes comma-separated integers")
+        if len(args.prompt_lengths) != args.batch_size or min(args.prompt_lengths) < 1:
+            p.error("--prompt-lengths needs one positive length per sequence of --batch-size")
+        if any(m.startswith("hf_") for m in args.modes.split(",")):
+            p.error("--prompt-lengths is for the LitGPT modes")
+        args.prompt_len = max(args.prompt_lengths)
+    elif args.batch_size != 1 and any(m.startswith("hf_") for m in args.modes.split(",")):
+        p.error("--batch-size is for the LitGPT modes")
     results = []
     ref = {}  # model family -> tokens of its eager mode
     for mode in args.modes.split(","):

@@ -13,6 +13,9 @@ checkpoints offline) with its static KV cache, so every mode runs the same model
 Per iteration: one prefill of ``--input-length`` tokens for ``--batch-size`` sequences (TTFT =
 its latency, including the first sampled token), then ``--output-length - 1`` decode steps
 (TBOT = mean latency of one decode step).  Every phase is bracketed by device synchronisation.
+``--prompt-lengths a,b,c,...`` (one per sequence) makes the batch ragged: the prompt is right-padded to the longest
+length (which replaces ``--input-length``), the first token of sequence b comes from its own last prompt position,
+and every decode step runs at per-sequence positions (an int64 ``[B, 1]`` tensor advanced in place).
 Prints one JSON line per mode with mean / median / p90 over ``--num-iterations`` iterations
 after ``--warmup-iterations`` untimed ones.
 """
@@ -75,16 +78,26 @@ def run(mode: str, args) -> dict:
     gen = torch.Generator(device).manual_seed(1)
     prompt = torch.randint(0, cfg.vocab_size, (args.batch_size, args.input_length), device=device, generator=gen)
     prefill_pos = torch.arange(args.input_length, device=device)
-    pos = torch.empty(1, dtype=torch.int64, device=device)
+    ragged = args.prompt_lengths is not None
+    if ragged:
+        lengths = torch.tensor(args.prompt_lengths, dtype=torch.int64, device=device)
+        last = lengths - 1
+        rows = torch.arange(args.batch_size, device=device)
+        pos = torch.empty((args.batch_size, 1), dtype=torch.int64, device=device)
+    else:
+        pos = torch.empty(1, dtype=torch.int64, device=device)
 
     def iteration():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         logits = fwd(prompt, prefill_pos)
-        tok = argmax_last(logits[:, -1], keepdim=True)
+        tok = argmax_last(logits[rows, last] if ragged else logits[:, -1], keepdim=True)
         torch.cuda.synchronize()
         ttft = time.perf_counter() - t0
-        pos.fill_(args.input_length)
+        if ragged:
+            pos.copy_(lengths.view(-1, 1))
+        else:
+            pos.fill_(args.input_length)
         steps = []
         for _ in range(args.output_length - 1):
             t1 = time.perf_counter()
@@ -121,6 +134,7 @@ def run(mode: str, args) -> dict:
         "latency_ms_per_request": round(1e3 * statistics.mean(totals), 2),
         "first_call_s": round(first, 2),
         "batch_size": B, "input_length": args.input_length, "output_length": n_out,
+        "prompt_lengths": args.prompt_lengths,
         "dtype": "bf16", "kv_cache_dtype": args.kv_cache_dtype,
         "kv_cache_gib": round(sum(c.numel() * c.element_size() for b in model.transformer.h
                                   for c in b.attn.kv_cache.buffers()) / 2 ** 30, 3),  # scale buffers included
@@ -143,9 +157,20 @@ def main(argv=None):
     p.add_argument("--kv-cache-dtype", choices=sorted(KV_CACHE_FORMATS), default="model",
                    help="'fp8' keeps the static KV cache as unscaled e4m3 (half the bytes), 'fp8-row' as e4m3 "
                         "with one power-of-two scale byte per (token, kv head) row")
+    p.add_argument("--prompt-lengths", default=None,
+                   help="a,b,c,...: one prompt length per sequence (a ragged batch, right-padded to the longest); "
+                        "--batch-size must match")
     args = p.parse_args(argv)
     if args.output_length < 1:
         p.error("--output-length must be >= 1")
+    if args.prompt_lengths is not None:
+        try:
+            args.prompt_lengths = [int(x) for x in args.prompt_lengths.split(",")]
+        except ValueError:
+            p.error("--prompt-lengths takes comma-separated integers")
+        if len(args.prompt_lengths) != args.batch_size or min(args.prompt_lengths) < 1:
+            p.error("--prompt-lengths needs one positive length per sequence of --batch-size")
+        args.input_length = max(args.prompt_lengths)
     for mode in args.modes.split(","):
         print(json.dumps(run(mode, args)), flush=True)
         torch.cuda.empty_cache()

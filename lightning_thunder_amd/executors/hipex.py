@@ -961,6 +961,52 @@ def _qkv_rope_cache_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, ro
 hip_qkv_rope_cache_s8 = ex.register_operator("hip_qkv_rope_cache_s8", meta=_qkv_rope_cache_s8_meta,
                                              fn=_qkv_rope_cache_s8_impl, tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
 hip_qkv_rope_cache_s8.written_args = (7, 8, 9, 10)  # kc, vc, k_scale, v_scale
+
+
+# Ragged batches: one int64 position per (sequence, token), ``pos`` [B, T], with cos / sin [B, T, rope_n] gathered per
+# token (ops/kv_rows.py).  The operators mirror the two above, over the per-row entries of csrc/rope.hip.
+def _qkv_rope_cache_rows_run(rope_args, caches, pos, stored):
+    """As ``_qkv_rope_cache_run`` for per-row positions: the kernel where ``qkv_rope_cache_rows_supported`` takes the
+    operands, else the program as the model spells it (RoPE, then one row write per buffer)."""
+    from ..ops.fused import qkv_rope_cache_rows_fwd, qkv_rope_cache_rows_supported
+    from ..ops.kv_rows import write_rows
+
+    qkv, cos, sin, _, n_query_groups, head_size, rope_n = rope_args
+    if qkv_rope_cache_rows_supported(qkv, cos, sin, caches[0], caches[1], pos, n_query_groups, head_size, rope_n,
+                                     *caches[2:]):
+        return qkv_rope_cache_rows_fwd(*rope_args, *caches[:2], pos, *caches[2:])
+    q, k, v = _qkv_rope_impl(*rope_args)
+    srcs = (t for pair in zip(stored(k), stored(v)) for t in pair)
+    return (q, *(write_rows(c, pos, t) for c, t in zip(caches, srcs)))
+
+
+def _qkv_rope_cache_rows_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
+    from ..ops.kv8 import e4m3_bytes
+
+    kv8 = kc.dtype == torch.uint8
+    if kv8 != (vc.dtype == torch.uint8):
+        raise ValueError("hip_qkv_rope_cache_rows: one of the two caches is uint8 (e4m3), the other is not")
+    return _qkv_rope_cache_rows_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n), (kc, vc), pos,
+                                    (lambda t: (e4m3_bytes(t),)) if kv8 else (lambda t: (t,)))
+
+
+def _qkv_rope_cache_rows_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, k_scale, v_scale,
+                                 pos):
+    from ..ops.kv8 import quantise_rows
+
+    return _qkv_rope_cache_rows_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n),
+                                    (kc, vc, k_scale, v_scale), pos, quantise_rows)
+
+
+hip_qkv_rope_cache_rows = ex.register_operator("hip_qkv_rope_cache_rows", meta=_qkv_rope_cache_meta,
+                                               fn=_qkv_rope_cache_rows_impl, tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
+hip_qkv_rope_cache_rows.written_args = (7, 8)
+hip_qkv_rope_cache_rows_s8 = ex.register_operator("hip_qkv_rope_cache_rows_s8", meta=_qkv_rope_cache_s8_meta,
+                                                  fn=_qkv_rope_cache_rows_s8_impl,
+                                                  tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
+hip_qkv_rope_cache_rows_s8.written_args = (7, 8, 9, 10)
+_KV_POSITION_MASK_IDS = ("custom_op.lta::kv_position_mask", "custom_op.custom_op_impl_custom_op_lta_kv_position_mask")
+_CACHE_WRITES = ("index_copy_inplace", "scatter_rows_inplace")  # shared positions / one position per token
 _KV8_QUANTISE_IDS = ("custom_op.lta::kv8_quantise_rows", "custom_op.custom_op_impl_custom_op_lta_kv8_quantise_rows")
 _KV8_DEQUANTISE_IDS = ("custom_op.lta::kv8_dequantise_rows",
                        "custom_op.custom_op_impl_custom_op_lta_kv8_dequantise_rows")
@@ -970,6 +1016,12 @@ def _kv8_fusion_off() -> bool:
     """LTA_KV8_FUSION=0 keeps the e4m3 KV cache's quantising writes and dequantising reads as the
     separate operations the model spells (A/B against the two fused kernels)."""
     return os.environ.get("LTA_KV8_FUSION", "1") == "0"
+
+
+def _kv_pos_fusion_off() -> bool:
+    """LTA_KV_POS_FUSION=0 keeps a ragged batch's position mask and per-row cache writes as the separate operations
+    the model spells (A/B against the per-row RoPE write and the position mode of the decode kernels)."""
+    return os.environ.get("LTA_KV_POS_FUSION", "1") == "0"
 
 
 def _only_tensor_arg(b, rest=0):
@@ -1014,7 +1066,7 @@ def _cache_sources(rw, t):
     else, and for both e4m3 kinds under LTA_KV8_FUSION=0."""
     (j,) = rw.consumers(t)
     b = rw.bsyms[j]
-    if b.sym.name == "index_copy_inplace":
+    if b.sym.name in _CACHE_WRITES:
         return "plain", (t,), ()
     if _kv8_fusion_off():
         return None
@@ -1042,7 +1094,11 @@ def _fuse_kv_cache_writes(trace):
 
     k and v must reach their caches the same way (``_cache_sources``), and every copied tensor is read
     once, by an ``index_copy_inplace`` along dim 2 at one int64 ``pos`` into a buffer of its dtype.
-    Anything else (a result read twice, another position, v through another format) stays."""
+    Anything else (a result read twice, another position, v through another format) stays.
+
+    A ragged batch the same way: the RoPE takes cos / sin ``[B, T, rope_n]``, every copied tensor is read once by a
+    ``scatter_rows_inplace`` at one int64 ``pos`` ``[B, T]``, and the result is ``hip_qkv_rope_cache_rows`` (or
+    ``hip_qkv_rope_cache_rows_s8``).  LTA_KV_POS_FUSION=0 leaves those writes alone."""
     rw = Rewrite(trace, ex)
     for i, b in enumerate(rw.bsyms):
         if b.sym is not hip_qkv_rope:
@@ -1055,22 +1111,27 @@ def _fuse_kv_cache_writes(trace):
             continue
         srcs = [t for pair in zip(sk[1], sv[1]) for t in pair]  # the operators' order: k, v, then their scales
         copies, pos = [], None
+        rows = getattr(b.args[1], "ndim", 2) == 3  # cos [B, T, rope_n]: one position per token
+        if rows and _kv_pos_fusion_off():
+            continue
         for t in srcs:
             if rw.uses(t) != 1:
                 break
             (j,) = rw.consumers(t)
             c = rw.bsyms[j]
-            if rw.touched(j) or c.sym.name != "index_copy_inplace":
+            if rw.touched(j) or c.sym.name != _CACHE_WRITES[rows]:
                 break
             w = operands(c)
-            buf = w["buf"]
-            if w["dim"] != 2 or w["src"] is not t or not isinstance(buf, TensorProxy) or buf.dtype != t.dtype:
+            buf, index = w["buf"], w["pos" if rows else "index"]
+            if not rows and w["dim"] != 2:
+                break
+            if w["src"] is not t or not isinstance(buf, TensorProxy) or buf.dtype != t.dtype:
                 break
             if pos is None:
-                pos = w["index"]
-                if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64:
+                pos = index
+                if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or (rows and pos.ndim != 2):
                     break
-            elif getattr(w["index"], "name", None) != pos.name:
+            elif getattr(index, "name", None) != pos.name:
                 break
             copies.append((j, c.output, buf))
         if len(copies) != len(srcs):
@@ -1089,7 +1150,8 @@ def _fuse_kv_cache_writes(trace):
             lo = min(at_copies)
             if any(lo < j < at and j not in at_copies for t in (*outs, *bufs) for j in rw.consumers(t)):
                 continue
-        op = hip_qkv_rope_cache_s8 if sk[0] == "scaled" else hip_qkv_rope_cache
+        op = ((hip_qkv_rope_cache, hip_qkv_rope_cache_s8),
+              (hip_qkv_rope_cache_rows, hip_qkv_rope_cache_rows_s8))[rows][sk[0] == "scaled"]
         rw.replace(at, op.bind(*b.args, *bufs, pos, output=(q, *outs)))
         rw.drop(*({i, *sk[2], *sv[2], *at_copies} - {at}))
     return rw.finish(f"hipex: {rw.replaced} KV-cache write pair(s) fused into RoPE")
@@ -1133,6 +1195,42 @@ def _kv8_rows_dequantised(rw, t, dtype):
     return (c, s), j, (j,)
 
 
+def _fuse_kv_position_reads(trace):
+    """``mask = kv_position_mask(pos, S); hip_decode_attn(q, k, v, mask, False, scale)`` with ``S`` the keys' and
+    ``pos`` int64 ``[B, T]`` -> ``hip_decode_attn_pos(q, k, v, pos, scale)``: the kernel takes every row's key count
+    from its position, reads no mask and splits the row's live keys over all of its workgroups.  The mask is shared
+    by the layers of a step: it must be read by such attentions only, and is dropped with the last of them."""
+    if _kv_pos_fusion_off():
+        return trace
+    rw = Rewrite(trace, ex)
+    for m, b in enumerate(rw.bsyms):
+        if b.sym.id not in _KV_POSITION_MASK_IDS or rw.touched(m):
+            continue
+        p = operands(b, ("input_pos", "S"))
+        pos, S, mask = p["input_pos"], p["S"], b.output
+        if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or pos.ndim != 2 or isinstance(S, TensorProxy):
+            continue
+        readers = rw.consumers(mask)
+        found = []
+        for i in readers:
+            a = rw.bsyms[i]
+            if a.sym is not hip_decode_attn or rw.touched(i) or readers.count(i) != 1:
+                break
+            o = operands(a)
+            q, k = o["q"], o["k"]
+            if o["mask"] is not mask or o["causal"] or k.shape[2] != int(S):
+                break
+            if tuple(pos.shape) != (q.shape[0], q.shape[2]):
+                break
+            found.append((i, a, o))
+        if not found or len(found) != len(readers):
+            continue
+        for i, a, o in found:
+            rw.replace(i, hip_decode_attn_pos.bind(o["q"], o["k"], o["v"], pos, o["scale"], output=a.output))
+        rw.drop(m)
+    return rw.finish(f"hipex: {rw.replaced} decode attention(s) take their key counts from the positions")
+
+
 def _fuse_kv8_reads(trace):
     """``hip_decode_attn(q, to(view(kc, float8_e4m3fn), q.dtype), to(view(vc, float8_e4m3fn), q.dtype), ...)``
     over uint8 caches -> ``hip_decode_attn_kv8(q, kc, vc, ...)``: the decode kernel unpacks the e4m3
@@ -1142,16 +1240,20 @@ def _fuse_kv8_reads(trace):
     The scaled cache the same way: ``hip_decode_attn(q, kv8_dequantise_rows(kc, ks, q.dtype),
     kv8_dequantise_rows(vc, vs, q.dtype), ...)`` -> ``hip_decode_attn_kv8s(q, kc, vc, ks, vs, ...)``.  k and v
     must be of one kind, and nothing may write a byte or scale cache in place between its dequantise and
-    the attention."""
+    the attention.
+
+    ``hip_decode_attn_pos`` folds the same chains into ``hip_decode_attn_kv8_pos`` / ``hip_decode_attn_kv8s_pos``."""
     if _kv8_fusion_off():
         return trace
     rw = Rewrite(trace, ex)
     for i, b in enumerate(rw.bsyms):
-        if b.sym is not hip_decode_attn:
+        if b.sym is not hip_decode_attn and b.sym is not hip_decode_attn_pos:
             continue
+        by_pos = b.sym is hip_decode_attn_pos
         p = operands(b)
         q = p["q"]
-        for op, resolve in ((hip_decode_attn_kv8s, _kv8_rows_dequantised), (hip_decode_attn_kv8, _e4m3_dequantised)):
+        for op, resolve in (((hip_decode_attn_kv8s, hip_decode_attn_kv8s_pos)[by_pos], _kv8_rows_dequantised),
+                            ((hip_decode_attn_kv8, hip_decode_attn_kv8_pos)[by_pos], _e4m3_dequantised)):
             rk, rv = resolve(rw, p["k"], q.dtype), resolve(rw, p["v"], q.dtype)
             if rk is not None and rv is not None:
                 break
@@ -1163,7 +1265,8 @@ def _fuse_kv8_reads(trace):
         if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
                for c in caches for j in rw.consumers(c)):
             continue
-        rw.replace(i, op.bind(q, *caches, p["mask"], p["causal"], p["scale"], output=b.output))
+        rest = (p["pos"], p["scale"]) if by_pos else (p["mask"], p["causal"], p["scale"])
+        rw.replace(i, op.bind(q, *caches, *rest, output=b.output))
         for _, _, links in (rk, rv):
             for j in links:
                 if rw.uses(rw.bsyms[j].output) != 1:
@@ -1321,6 +1424,8 @@ def _rope_of_gemm(rw, i, b, gemm):
     if not all(isinstance(r[k], int) for k in ("n_head", "n_query_groups", "head_size", "rope_n")):
         return None
     if rw.producer(r["cos"], -1) > j or rw.producer(r["sin"], -1) > j:
+        return None
+    if getattr(r["cos"], "ndim", 2) != 2:  # per-token rotations (a ragged batch): the epilogue indexes cos by t
         return None
     return j, r
 
@@ -1559,7 +1664,7 @@ _PASSES = (
     partial(_fuse_decode, kind=_MXFP4_DECODE, folds=("gate", "act", "residual", "norm", "group"),
             message="hipex: MXFP4 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
                     "{norm} norm prologue(s), {group} group(s))"),
-    _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv8_reads,
+    _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv_position_reads, _fuse_kv8_reads,
     partial(_fuse_decode, kind=_BF16_DECODE, folds=("group",), message="hipex: {group} grouped decode projection launch(es)"),
     _fuse_qkv_rope_gemm, _fuse_fp8_qkv_rope_gemm, _fuse_attn_bwd_rope,
 )
@@ -1733,8 +1838,10 @@ def _qkv_rope_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n):
 
 
 def _qkv_rope_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n):
-    from ..ops.fused import qkv_rope_fwd
+    from ..ops.fused import qkv_rope_fwd, qkv_rope_rows_fwd
 
+    if cos.dim() == 3:  # one rotation per (sequence, token): a ragged batch
+        return qkv_rope_rows_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
     return qkv_rope_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n)
 
 
@@ -1770,11 +1877,14 @@ def qkv_split_rope_lookaside(qkv, cos, sin, n_head, n_query_groups, head_size, r
         and head_size % 8 == 0
         and rope_n_elem % 16 == 0
         and rope_n_elem <= head_size
-        and cos.ndim == 2
-        and cos.shape[0] >= qkv.shape[1]
-        and cos.shape[1] == rope_n_elem
+        and cos.ndim in (2, 3)
+        and cos.shape[-2] >= qkv.shape[1]
+        and cos.shape[-1] == rope_n_elem
         and cos.dtype in (torch.float32, qkv.dtype)
     )
+    if ok and cos.ndim == 3:  # [B, T, rope_n], one rotation per token (a ragged batch): forward only
+        ok = (tuple(cos.shape) == (qkv.shape[0], qkv.shape[1], rope_n_elem) and tuple(sin.shape) == tuple(cos.shape)
+              and not qkv.requires_grad)
     if not ok:
         return qkv_split_rope_lookaside.__wrapped_original__(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n_elem)
     return hip_qkv_rope(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n_elem)
@@ -1980,6 +2090,52 @@ def _decode_attn_kv8s_impl(q, k8, v8, k_scale, v_scale, mask, causal, scale):
 
 hip_decode_attn_kv8s = ex.register_operator("hip_decode_attn_kv8s", meta=_decode_attn_kv8s_meta,
                                             fn=_decode_attn_kv8s_impl)
+
+
+# The position forms (a ragged batch): ``pos`` int64 [B, T] in place of mask and causal flag.
+def _decode_attn_pos_meta(q, k, v, pos, scale):
+    return TensorProxy(like=q)
+
+
+def _decode_attn_pos_impl(q, k, v, pos, scale):
+    from ..ops.attention import decode_attn, decode_attn_pos, decode_attn_pos_supported
+    from ..ops.kv_rows import position_mask
+
+    if decode_attn_pos_supported(q, k, v, pos):
+        return decode_attn_pos(q, k, v, pos, scale)
+    return decode_attn(q, k, v, position_mask(pos, k.shape[2]), False, scale)
+
+
+def _decode_attn_e4m3_pos_run(q, caches, pos, scale, supported, kernel, dequantise):
+    """As ``_decode_attn_e4m3_run``: ``kernel`` where ``supported`` takes the operands, else the program as the model
+    spells it, ``dequantise`` and the 16-bit position operator."""
+    if supported(q, *caches, pos):
+        return kernel(q, *caches, pos, scale)
+    return _decode_attn_pos_impl(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), pos, scale)
+
+
+def _decode_attn_kv8_pos_impl(q, k8, v8, pos, scale):
+    from ..ops.attention import decode_attn_kv8_pos, decode_attn_kv8_pos_supported
+    from ..ops.kv8 import e4m3_values
+
+    return _decode_attn_e4m3_pos_run(q, (k8, v8), pos, scale, decode_attn_kv8_pos_supported, decode_attn_kv8_pos,
+                                     e4m3_values)
+
+
+def _decode_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale):
+    from ..ops.attention import decode_attn_kv8s_pos, decode_attn_kv8s_pos_supported
+    from ..ops.kv8 import dequantise_rows
+
+    return _decode_attn_e4m3_pos_run(q, (k8, v8, k_scale, v_scale), pos, scale, decode_attn_kv8s_pos_supported,
+                                     decode_attn_kv8s_pos, dequantise_rows)
+
+
+hip_decode_attn_pos = ex.register_operator("hip_decode_attn_pos", meta=_decode_attn_pos_meta, fn=_decode_attn_pos_impl)
+hip_decode_attn_kv8_pos = ex.register_operator("hip_decode_attn_kv8_pos", meta=_decode_attn_pos_meta,
+                                               fn=_decode_attn_kv8_pos_impl)
+hip_decode_attn_kv8s_pos = ex.register_operator(
+    "hip_decode_attn_kv8s_pos", meta=lambda q, k8, v8, k_scale, v_scale, pos, scale: TensorProxy(like=q),
+    fn=_decode_attn_kv8s_pos_impl)
 
 
 def _broadcastable(shape, target) -> bool:

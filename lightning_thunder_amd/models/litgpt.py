@@ -22,6 +22,7 @@ import torch.utils.checkpoint
 import torch.nn.functional as F
 
 from ..ops.kv8 import kv8_dequantise_rows, kv8_quantise_rows
+from ..ops.kv_rows import kv_position_mask
 
 
 @dataclass
@@ -145,7 +146,11 @@ def build_rope_cache(seq_len: int, n_elem: int, device=None, base: int = 10000, 
 
 
 def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> torch.Tensor:
-    """x: [B, H, T, hs]; cos/sin: [T, hs]  (LitGPT's rotate-half formulation)."""
+    """x: [B, H, T, hs]; cos/sin: [T, hs], or [B, T, hs] gathered per sequence (a ragged batch), which
+    broadcast over the heads  (LitGPT's rotate-half formulation)."""
+    if cos.dim() == 3:
+        cos = cos.unsqueeze(1)
+        sin = sin.unsqueeze(1)
     head_size = x.size(-1)
     x1 = x[..., : head_size // 2]
     x2 = x[..., head_size // 2:]
@@ -217,7 +222,10 @@ class KVCache(nn.Module):
     ``ops/kv8.py``: the buffers ``k_scale`` / ``v_scale`` (uint8 ``[B, n_query_groups, max_seq, 1]``,
     ``e + 127``, initialised to 127) hold the rows' exponents and the bytes hold ``x * 2^-e``, so the e4m3
     rounding error is the same relative 2^-4 at every magnitude from 2^-24 to 57344 and no calibration is
-    needed.  ``scale=None`` is the unscaled cache."""
+    needed.  ``scale=None`` is the unscaled cache.
+
+    ``input_pos`` is the shared 1-D ``[T]`` (every sequence writes rows ``input_pos``), or int64 ``[B, T]`` for
+    a ragged batch: token (b, t) writes row ``input_pos[b, t]`` of sequence b, in every buffer of the format."""
 
     def __init__(self, k_shape, v_shape, device=None, dtype=None, scale: Optional[str] = None):
         super().__init__()
@@ -238,6 +246,8 @@ class KVCache(nn.Module):
                                      persistent=False)
 
     def forward(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        if input_pos.dim() == 2:
+            return self._forward_rows(input_pos, k, v)
         if self.scale is not None:
             k8, ks = kv8_quantise_rows(k)
             v8, vs = kv8_quantise_rows(v)
@@ -256,6 +266,26 @@ class KVCache(nn.Module):
         k_all = self.k.index_copy_(2, input_pos, k.to(self.k.dtype))
         v_all = self.v.index_copy_(2, input_pos, v.to(self.v.dtype))
         return k_all, v_all
+
+    def _forward_rows(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        """``forward`` with per-sequence positions: the same formats, each buffer written with one O(tokens)
+        ``scatter_`` along the key dim (LitGPT's spelling of the batched write)."""
+        def put(cache, src):
+            return cache.scatter_(2, input_pos[:, None, :, None].expand_as(src), src)
+
+        if self.scale is not None:
+            k8, ks = kv8_quantise_rows(k)
+            v8, vs = kv8_quantise_rows(v)
+            k_all, v_all = put(self.k, k8), put(self.v, v8)
+            ks_all, vs_all = put(self.k_scale, ks), put(self.v_scale, vs)
+            return kv8_dequantise_rows(k_all, ks_all, k.dtype), kv8_dequantise_rows(v_all, vs_all, v.dtype)
+        if self.k.dtype == torch.uint8:
+            f8 = torch.float8_e4m3fn
+            k8 = k.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
+            v8 = v.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
+            k_all, v_all = put(self.k, k8), put(self.v, v8)
+            return k_all.view(f8).to(k.dtype), v_all.view(f8).to(v.dtype)
+        return put(self.k, k.to(self.k.dtype)), put(self.v, v.to(self.v.dtype))
 
     def reset_parameters(self) -> None:
         torch.nn.init.zeros_(self.k)
@@ -466,7 +496,13 @@ class GPT(nn.Module):
         T = idx.size(1)
         if self.cos.numel() == 0 or self.cos.shape[0] < T:
             raise RuntimeError("call model.set_rope_cache(seq_len, device) before forward")
-        if input_pos is not None:  # incremental decoding against the KV cache
+        if input_pos is not None and input_pos.dim() == 2:  # a ragged batch: one position per (sequence, token)
+            B = idx.size(0)
+            flat = input_pos.reshape(-1)
+            cos = self.cos.index_select(0, flat).view(B, T, -1)
+            sin = self.sin.index_select(0, flat).view(B, T, -1)
+            mask = kv_position_mask(input_pos, self.max_seq_length)
+        elif input_pos is not None:  # incremental decoding against the KV cache
             cos = self.cos.index_select(0, input_pos)
             sin = self.sin.index_select(0, input_pos)
             mask = self.mask_cache.index_select(2, input_pos)
@@ -527,7 +563,8 @@ def flops_per_token(config: Config, seq_len: int, training: bool = True) -> floa
 
 @torch.no_grad()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, temperature: float = 0.0,
-             top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id: Optional[int] = None) -> torch.Tensor:
+             top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id: Optional[int] = None,
+             prompt_lengths: Optional[torch.Tensor] = None, pad_id: int = 0) -> torch.Tensor:
     """Autoregressive generation with the static KV cache (LitGPT ``generate``).
 
     ``forward`` is the callable used for every step (default: ``model``; pass ``thunder.jit(model)``).
@@ -539,10 +576,16 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
     then the nucleus ``top_p``, then one draw from the softmax of what is left.  The draws come from the
     project's Philox counter stream (``core.rng``), not from ATen's generator: ``torch.manual_seed(s)``
     before the call reproduces the tokens.  Returns ``[B, T + max_new_tokens]`` token ids.
+
+    ``prompt_lengths`` (int64 ``[B]``, ``1 <= len_b <= T``) makes the batch ragged: ``prompt`` is right-padded
+    and row b holds ``len_b`` real tokens; see :func:`_generate_ragged`.  ``pad_id`` is only used there.
     """
     from ..ops.sampling import argmax_last, sample_last
 
     forward = forward or model
+    if prompt_lengths is not None:
+        return _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k, top_p, eos_id,
+                                prompt_lengths, pad_id)
     B, T = prompt.shape
     if model.transformer.h[0].attn.kv_cache is None:
         raise RuntimeError("call model.set_kv_cache(batch_size, max_seq_length) first")
@@ -564,3 +607,58 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
             logits = forward(nxt, pos)
             pos.add_(1)
     return torch.cat(out, dim=1)
+
+
+def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k, top_p, eos_id, prompt_lengths,
+                     pad_id) -> torch.Tensor:
+    """``generate`` for a right-padded ``[B, Tmax]`` prompt whose row b holds ``prompt_lengths[b]`` tokens.
+
+    Prefill runs the padded prompt at the shared ``arange(Tmax)``: a pad token writes K/V rows at positions
+    ``>= len_b``, and each of those is overwritten by the sequence's own token before any row can attend to it,
+    because a row at position p sees keys ``<= p`` only.  The first token of row b comes from
+    ``logits[b, len_b - 1]``.  Every decode step feeds ``[B, 1]`` tokens with one int64 ``[B, 1]`` position
+    tensor that starts at ``prompt_lengths`` and is advanced in place (fixed addresses: a hipGraph replays).
+    A sequence that has produced ``eos_id`` keeps riding in the batch, its later tokens are ``pad_id``; the
+    loop ends when all are done.  Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
+    from column ``len_b`` on, then ``pad_id``."""
+    from ..ops.sampling import argmax_last, sample_last
+
+    B, T = prompt.shape
+    cache = model.transformer.h[0].attn.kv_cache
+    if cache is None:
+        raise RuntimeError("call model.set_kv_cache(batch_size, max_seq_length) first")
+    device = prompt.device
+    lengths = torch.as_tensor(prompt_lengths, device=device).to(torch.int64).reshape(-1)
+    if lengths.numel() != B:
+        raise ValueError(f"generate: prompt_lengths has {lengths.numel()} entries for a batch of {B}")
+    lo, hi = int(lengths.min()), int(lengths.max())
+    if lo < 1 or hi > T:
+        raise ValueError(f"generate: prompt_lengths must lie in [1, {T}], got {lo} .. {hi}")
+    if hi + max_new_tokens > cache.k.shape[2]:
+        raise ValueError(f"generate: the longest prompt ({hi}) plus {max_new_tokens} new tokens exceeds the KV "
+                         f"cache of {cache.k.shape[2]} positions")
+    out = torch.full((B, T + max_new_tokens), pad_id, device=device, dtype=prompt.dtype)
+    cols = torch.arange(T, device=device)
+    out[:, :T] = torch.where(cols[None, :] < lengths[:, None], prompt, torch.full_like(prompt, pad_id))
+    if max_new_tokens <= 0:
+        return out
+    logits = forward(prompt, torch.arange(T, device=device))
+    last = logits[torch.arange(B, device=device), lengths - 1]
+    pos = lengths.clone().view(B, 1)  # where the next token of every sequence goes; advanced in place
+    done = torch.zeros(B, 1, device=device, dtype=torch.bool)
+    for i in range(max_new_tokens):
+        if temperature > 0:
+            nxt = sample_last(last, temperature, top_k, top_p, keepdim=True)
+        else:
+            nxt = argmax_last(last, keepdim=True)
+        nxt = torch.where(done, torch.full_like(nxt, pad_id), nxt)
+        out.scatter_(1, pos, nxt.to(out.dtype))
+        if eos_id is not None:
+            done = done | (nxt == eos_id)
+            if bool(done.all()):
+                break
+        if i + 1 < max_new_tokens:
+            logits = forward(nxt, pos)
+            last = logits[:, -1]
+            pos.add_(1)
+    return out

@@ -481,3 +481,96 @@ def decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask=None, causal: bool = Fals
                          f"{None if v_scale is None else (v_scale.dtype, tuple(v_scale.shape))}")
     q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
     return _decode_launch("lta_decode_attn_kv8s", q, k8, v8, mask, causal, scale, scales=(k_scale, v_scale))
+
+
+# ------------------------------------------------------------------------------------------------
+# Position mode of the decode kernels (ragged batches): every row's key count from pos[b, t], no mask
+# ------------------------------------------------------------------------------------------------
+# the position entries: pointers q, k, v, <scale caches>, pos, o, ws_acc, ws_ml
+for _entry, _scale_ptrs in (("lta_decode_attn_pos", 0), ("lta_decode_attn_kv8_pos", 0), ("lta_decode_attn_kv8s_pos", 2)):
+    register_signature(_entry, [c_int, *[c_void_p] * (7 + _scale_ptrs), *[c_int] * 6, c_void_p, c_int, c_float, c_int,
+                                c_void_p])
+
+
+def _pos_ok(q, k, pos) -> bool:
+    """int64 positions [B, T] (any strides) on q's device, at most DECODE_MAX_QUERIES query rows."""
+    return (pos is not None and pos.dtype == torch.int64 and pos.dim() == 2 and q.dim() == 4 and k.dim() == 4
+            and tuple(pos.shape) == (q.shape[0], q.shape[2]) and pos.device == q.device
+            and 0 < q.shape[2] <= DECODE_MAX_QUERIES)
+
+
+def decode_attn_pos_supported(q, k, v, pos) -> bool:
+    """What the 16-bit position kernel takes: bf16 / fp16 q, k, v of one dtype and head dim 64 / 128, GQA
+    head counts, int64 ``pos`` [B, T] with T <= 16."""
+    return (_pos_ok(q, k, pos) and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype
+            and v.dtype == q.dtype and q.shape[-1] in (64, 128) and k.shape == v.shape and k.shape[-1] == q.shape[-1]
+            and k.shape[0] == q.shape[0] and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0)
+
+
+def decode_attn_kv8_pos_supported(q, k8, v8, pos) -> bool:
+    return _pos_ok(q, k8, pos) and decode_attn_kv8_supported(q, k8, v8)
+
+
+def decode_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos) -> bool:
+    return _pos_ok(q, k8, pos) and decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale)
+
+
+def _decode_pos_launch(entry: str, q, k, v, pos, scale: float | None, scales=None):
+    """One launch of a position entry.  The grid comes from the capacity S as for the mask entries
+    (``decode_launch_shape``): the positions stay on the device, so a hipGraph replays the launch while they
+    advance; the kernel splits each row's live range over the ``nsplit`` workgroups itself."""
+    lib = require()
+    B, Hq, T, D = q.shape
+    Hkv, S = k.shape[1], k.shape[2]
+    sc = scale if scale is not None else 1.0 / math.sqrt(D)
+    rows = B * Hq * T
+    wsplit, nsplit, _ = decode_launch_shape(rows, S)
+    o = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
+    ws_acc = ws_ml = None
+    if nsplit > 1:
+        ws_acc = torch.empty((nsplit, rows, D), device=q.device, dtype=torch.float32)
+        ws_ml = torch.empty((nsplit, rows, 2), device=q.device, dtype=torch.float32)
+    extra = () if scales is None else (*scales[0].stride()[:3], *scales[1].stride()[:3])
+    st = (ctypes.c_int64 * (11 + len(extra)))(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
+                                              k.stride(2), v.stride(0), v.stride(1), v.stride(2), pos.stride(0),
+                                              pos.stride(1), *extra)
+    sptrs = () if scales is None else (ptr(scales[0]), ptr(scales[1]))
+    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *sptrs, ptr(pos), ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq,
+                             Hkv, T, S, D, ctypes.cast(st, ctypes.c_void_p), nsplit, float(sc), int(wsplit),
+                             stream_ptr(q.device))
+    check(rc, entry)
+    return o
+
+
+def decode_attn_pos(q, k, v, pos, scale: float | None = None):
+    """Decode attention of a ragged batch: q [B, Hq, T, D] (T <= 16), k / v [B, Hkv, S, D], ``pos`` int64
+    [B, T].  Row (b, hq, t) attends keys ``0 .. n-1`` with ``n = clamp(pos[b, t] + 1, 0, S)``: what
+    ``decode_attn`` computes under the mask ``arange(S) <= pos[b, t]``, without the mask tensor and with the
+    row's live keys split over all of its workgroups.  ``n = 0`` gives a NaN row, like a fully masked one."""
+    if not decode_attn_pos_supported(q, k, v, pos):
+        raise ValueError(f"decode_attn_pos: unsupported operands q {q.dtype} {tuple(q.shape)}, k {k.dtype} "
+                         f"{tuple(k.shape)}, v {v.dtype} {tuple(v.shape)}, pos "
+                         f"{None if pos is None else (pos.dtype, tuple(pos.shape))}")
+    q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
+    return _decode_pos_launch("lta_decode_attn_pos", q, k, v, pos, scale)
+
+
+def decode_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None):
+    """``decode_attn_pos`` over an unscaled e4m3 cache (the operands of ``decode_attn_kv8``)."""
+    if not decode_attn_kv8_pos_supported(q, k8, v8, pos):
+        raise ValueError(f"decode_attn_kv8_pos: unsupported operands q {q.dtype} {tuple(q.shape)}, k {k8.dtype} "
+                         f"{tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, pos "
+                         f"{None if pos is None else (pos.dtype, tuple(pos.shape))}")
+    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
+    return _decode_pos_launch("lta_decode_attn_kv8_pos", q, k8, v8, pos, scale)
+
+
+def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None):
+    """``decode_attn_pos`` over the scaled e4m3 cache (the operands of ``decode_attn_kv8s``): equals
+    ``decode_attn_pos`` over the dequantised cache bit for bit, with that kernel's exclusions."""
+    if not decode_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
+        raise ValueError(f"decode_attn_kv8s_pos: unsupported operands q {q.dtype} {tuple(q.shape)}, k {k8.dtype} "
+                         f"{tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, pos "
+                         f"{None if pos is None else (pos.dtype, tuple(pos.shape))}")
+    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
+    return _decode_pos_launch("lta_decode_attn_kv8s_pos", q, k8, v8, pos, scale, scales=(k_scale, v_scale))

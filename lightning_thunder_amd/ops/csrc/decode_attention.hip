@@ -69,6 +69,15 @@ struct KVScales {
 };
 struct NoScales {};
 
+// Position mode (POS): no mask; row (b, hq, t) attends keys 0 .. n-1 with n = clamp(pos[b, t] + 1, 0, S), so a
+// ragged batch needs no [B, 1, T, S] mask tensor and a bad position never reads outside the cache.  Strides in
+// elements over b, t.
+struct RowPos {
+  const int64_t* pos;
+  int64_t sb, st;
+};
+struct NoPos {};
+
 // KS (with KV = uint8_t): the cache is the scaled one.  The lane that owns key j loads that key's two scale
 // bytes (consecutive bytes across the lanes of a 64-key block) and forms 2^e as byte << 23; the score is
 // dot * 2^ek and V is accumulated with p * 2^ev in place of p, while l keeps the unscaled p.  Both products
@@ -77,13 +86,22 @@ struct NoScales {};
 // subnormals and overflow (a partial sum below 2^-126 or above 2^127 after scaling rounds differently), and
 // an all-zero result (the sums start from the e4m3 kernels' -0).  A contraction of dot * 2^ek into the following subtraction
 // (v_fma) is harmless for the same reason: the product it skips rounding is exact.
-template <typename T, typename KV, int D, bool WSPLIT, bool KS = false>
+//
+// POS: the host still picks the grid from the capacity S (under a hipGraph it cannot know the positions), and
+// the kernel splits the row's live range 0 .. n-1 over the gridDim.y splits itself: chunk_row =
+// round_up(ceil(n / nsplit), 64), split s takes [s * chunk_row, min(n, (s + 1) * chunk_row)).  Every split of
+// a row then has work unless n is tiny; an empty one stores m = -inf, l = 0, which the combine kernel skips.
+// With n = S and the host's nsplit, chunk_row is the host's chunk, so the result equals the mask kernel's
+// under an all-true mask bit for bit.  `mask`, `chunk` and `causal` are unused.  All three position kernels
+// round acc / l as the 16-bit kernel does (`normalised` with its scaled-cache form), so both e4m3 ones equal
+// the 16-bit one over the dequantised cache bit for bit, with the exclusions above (a zero result's sign included).
+template <typename T, typename KV, int D, bool WSPLIT, bool KS = false, bool POS = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const T* __restrict__ q, const KV* __restrict__ k, const KV* __restrict__ v, const uint8_t* __restrict__ mask,
     T* __restrict__ o, float* __restrict__ ws_acc, float* __restrict__ ws_ml, int B, int Hq, int Hkv, int Tq, int S,
     int64_t qsb, int64_t qsh, int64_t qst, int64_t ksb, int64_t ksh, int64_t kss, int64_t vsb, int64_t vsh,
     int64_t vss, int64_t msb, int64_t msh, int64_t mst, int64_t mss, int chunk, int causal, float scale,
-    std::conditional_t<KS, KVScales, NoScales> sc) {
+    std::conditional_t<KS, KVScales, NoScales> sc, std::conditional_t<POS, RowPos, NoPos> rp) {
   static_assert(!KS || sizeof(KV) == 1, "scales belong to an e4m3 cache");
   constexpr int DPL = D / 64;          // output dims per lane after the final reduce-scatter
   constexpr bool kE4M3 = sizeof(KV) == 1;
@@ -98,9 +116,19 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   const int b = row / (Hq * Tq);
   const int hk = hq / (Hq / Hkv);
   const int split = blockIdx.y;
-  const int j_begin = split * chunk;
+  int j_begin = split * chunk;
   int j_end = min(S, j_begin + chunk);
   if (causal) j_end = min(j_end, t + 1);
+  if constexpr (POS) {
+    // a wave owns one row: its position is one scalar load (the row index made uniform for the compiler)
+    const int urow = __builtin_amdgcn_readfirstlane(row);
+    const int64_t p = rp.pos[(urow / (Hq * Tq)) * rp.sb + ((urow / Hq) % Tq) * rp.st];
+    const int n = (int)min(max(p + 1, (int64_t)0), (int64_t)S);
+    const int nsplit = gridDim.y;
+    const int chunk_row = ((n + nsplit - 1) / nsplit + 63) / 64 * 64;
+    j_begin = split * chunk_row;
+    j_end = min(n, j_begin + chunk_row);
+  }
 
   // scaled q row -> wave-private LDS (read back as broadcasts)
   const T* qrow = q + b * qsb + hq * qsh + t * qst;
@@ -108,7 +136,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   __builtin_amdgcn_wave_barrier();
   const KV* kbase = k + b * ksb + hk * ksh;
   const KV* vbase = v + b * vsb + hk * vsh;
-  const uint8_t* mrow = mask ? mask + b * msb + hq * msh + t * mst : nullptr;
+  [[maybe_unused]] const uint8_t* mrow = mask ? mask + b * msb + hq * msh + t * mst : nullptr;
   [[maybe_unused]] const uint8_t* ksrow = nullptr;
   [[maybe_unused]] const uint8_t* vsrow = nullptr;
   if constexpr (KS) {
@@ -126,7 +154,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   for (int j0 = j_begin + (WSPLIT ? w * 64 : 0); j0 < j_end; j0 += (WSPLIT ? kRowsPerBlock * 64 : 64)) {
     const int j = j0 + lane;
     bool valid = j < j_end;
-    if (valid && mrow) valid = mrow[(int64_t)j * mss] != 0;
+    if constexpr (!POS) {
+      if (valid && mrow) valid = mrow[(int64_t)j * mss] != 0;
+    }
     if (!__any(valid)) continue;  // fully masked block: no K/V traffic
     float s = -INFINITY;
     // scale bytes of key j's K row and V row: loaded ahead of the K row, turned into 2^e where first used
@@ -226,7 +256,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     const float inv = 1.f / l;  // fully masked row -> 0 * inf = nan, like PyTorch SDPA
     T* orow = o + (((int64_t)b * Hq + hq) * Tq + t) * D + lane * DPL;  // o is [B, Hq, Tq, D]
 #pragma unroll
-    for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
+    for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS || POS>(acc[i], inv);
   } else {
     float* wa = ws_acc + ((int64_t)split * rows + row) * D + lane * DPL;
 #pragma unroll
@@ -265,38 +295,39 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
 }
 
-template <typename T, typename KV, int D, bool KS = false>
+template <typename T, typename KV, int D, bool KS = false, bool POS = false>
 int launch(const void* q, const void* k, const void* v, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
            int Hq, int Hkv, int Tq, int S, const int64_t* st, int chunk, int nsplit, int causal, float scale,
-           int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc = {}) {
+           int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc = {},
+           std::conditional_t<POS, RowPos, NoPos> rp = {}) {
   const int rows = B * Tq * Hq;
   if (wsplit) {
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS, POS>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
                        (const KV*)k, (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
                        Tq, S, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11],
-                       st[12], chunk, causal, scale, sc);
+                       st[12], chunk, causal, scale, sc, rp);
   } else {
     dim3 grid((rows + kRowsPerBlock - 1) / kRowsPerBlock, nsplit);
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS, POS>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
                        (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
                        st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12],
-                       chunk, causal, scale, sc);
+                       chunk, causal, scale, sc, rp);
   }
   if (nsplit > 1)
-    hipLaunchKernelGGL((decode_attn_combine_kernel<T, KV, D, KS>), dim3(rows), dim3(64), 0, stream, (const float*)ws_acc,
+    hipLaunchKernelGGL((decode_attn_combine_kernel<T, KV, D, KS || POS>), dim3(rows), dim3(64), 0, stream, (const float*)ws_acc,
                        (const float*)ws_ml, (T*)o, rows, nsplit, Hq, Tq);
   return (int)hipGetLastError();
 }
 
 // `launch` for q / o of `dtype` and head dim D; KV = void: the cache holds q's type.  `a`: launch's arguments.
-template <typename KV, bool KS = false, typename... A>
+template <typename KV, bool KS = false, bool POS = false, typename... A>
 int dispatch(int dtype, int D, A... a) {
   using B16 = __hip_bfloat16;
   constexpr bool kSame = std::is_void_v<KV>;
-  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS>(a...);
-  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS>(a...);
-  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS>(a...);
-  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS>(a...);
+  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, POS>(a...);
+  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, POS>(a...);
+  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, POS>(a...);
+  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, POS>(a...);
   return (int)hipErrorInvalidValue;
 }
 
@@ -349,4 +380,55 @@ LTA_EXPORT int lta_decode_attn_kv8s(int dtype, const void* q, const void* k, con
                     strides[16], strides[17], strides[18]};
   return dispatch<uint8_t, true>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit,
                                  causal, scale, wsplit, (hipStream_t)stream, sc);
+}
+
+// The position entries: no mask and no causal flag; `pos` int64 [B, Tq] gives every row its key count (see
+// RowPos).  strides: q b,h,t | k b,h,s | v b,h,s | pos b,t (| k scale b,h,s | v scale b,h,s for the scaled cache).
+// `nsplit` is the host's split count for the capacity S; the kernel derives each row's own chunk from it.
+namespace lta {
+namespace {
+
+template <typename KV, bool KS>
+int launch_pos(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o, void* ws_acc,
+               void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int nsplit,
+               float scale, int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc) {
+  if (!sizes_ok(Hq, Hkv, 64, nsplit) || pos == nullptr || S < 0) return (int)hipErrorInvalidValue;
+  if (nsplit > 1 && (ws_acc == nullptr || ws_ml == nullptr)) return (int)hipErrorInvalidValue;
+  int64_t st[13] = {};  // the mask's four strides stay 0
+  for (int i = 0; i < 9; ++i) st[i] = strides[i];
+  const RowPos rp{(const int64_t*)pos, strides[9], strides[10]};
+  return dispatch<KV, KS, true>(dtype, D, q, k, v, (const void*)nullptr, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
+                                (const int64_t*)st, 0, nsplit, 0, scale, wsplit, stream, sc, rp);
+}
+
+}  // namespace
+}  // namespace lta
+
+LTA_EXPORT int lta_decode_attn_pos(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o,
+                                   void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                   const int64_t* strides, int nsplit, float scale, int wsplit, void* stream) {
+  using namespace lta;
+  return launch_pos<void, false>(dtype, q, k, v, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, D, strides, nsplit, scale,
+                                 wsplit, (hipStream_t)stream, NoScales{});
+}
+
+LTA_EXPORT int lta_decode_attn_kv8_pos(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o,
+                                       void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                       const int64_t* strides, int nsplit, float scale, int wsplit, void* stream) {
+  using namespace lta;
+  if (!e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
+  return launch_pos<uint8_t, false>(dtype, q, k, v, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, D, strides, nsplit,
+                                    scale, wsplit, (hipStream_t)stream, NoScales{});
+}
+
+LTA_EXPORT int lta_decode_attn_kv8s_pos(int dtype, const void* q, const void* k, const void* v, const void* k_scale,
+                                        const void* v_scale, const void* pos, void* o, void* ws_acc, void* ws_ml, int B,
+                                        int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int nsplit,
+                                        float scale, int wsplit, void* stream) {
+  using namespace lta;
+  if (!e4m3_cache_ok(k, v, strides) || k_scale == nullptr || v_scale == nullptr) return (int)hipErrorInvalidValue;
+  const KVScales sc{(const uint8_t*)k_scale, (const uint8_t*)v_scale, strides[11], strides[12], strides[13],
+                    strides[14], strides[15], strides[16]};
+  return launch_pos<uint8_t, true>(dtype, q, k, v, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, D, strides, nsplit, scale,
+                                   wsplit, (hipStream_t)stream, sc);
 }

@@ -22,12 +22,22 @@ struct KVDst {
   int64_t ksb, ksg, kss, vsb, vsg, vss;
 };
 
-template <typename T, typename C>
+// Per-row positions (ROWS, a ragged batch): cos / sin are [B*Tn, rope_n] and pos is [B*Tn], all indexed by
+// b * Tn + t where the shared-position kernels index by t.  S is the cache's capacity: a token whose position
+// is outside [0, S) writes no k / v row (and no scale byte), so a bad position never writes outside the cache;
+// its q row is stored as usual.
+struct RowsCap {
+  int S;
+};
+struct NoRows {};
+
+template <typename T, typename C, bool ROWS = false>
 __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const T* __restrict__ qkv, const C* __restrict__ cos_,
                                                            const C* __restrict__ sin_, T* __restrict__ q,
                                                            T* __restrict__ k, T* __restrict__ v,
                                                            const int64_t* __restrict__ pos, KVDst st, int B, int Tn,
-                                                           int nh, int ng, int hs, int rope_n) {
+                                                           int nh, int ng, int hs, int rope_n,
+                                                           std::conditional_t<ROWS, RowsCap, NoRows> rc) {
   constexpr int VW = Vec16<T>::N;
   const int chunks = hs / VW;
   const int heads = nh + 2 * ng;
@@ -48,11 +58,23 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const T* __restrict__
       dst = q + (((int64_t)b * nh + h) * Tn + t) * hs;
       rotate = true;
     } else if (h < nh + ng) {
-      const int64_t s = pos ? pos[t] : t;
+      int64_t s;
+      if constexpr (ROWS) {
+        s = pos[(int64_t)b * Tn + t];
+        if (s < 0 || s >= rc.S) continue;
+      } else {
+        s = pos ? pos[t] : t;
+      }
       dst = k + b * st.ksb + (h - nh) * st.ksg + s * st.kss;
       rotate = true;
     } else {
-      const int64_t s = pos ? pos[t] : t;
+      int64_t s;
+      if constexpr (ROWS) {
+        s = pos[(int64_t)b * Tn + t];
+        if (s < 0 || s >= rc.S) continue;
+      } else {
+        s = pos ? pos[t] : t;
+      }
       dst = v + b * st.vsb + (h - nh - ng) * st.vsg + s * st.vss;
       rotate = false;
     }
@@ -63,8 +85,9 @@ __global__ __launch_bounds__(256) void qkv_rope_fwd_kernel(const T* __restrict__
     if (d0 >= half) continue;  // handled together with its partner chunk
     const Vec16<T> x1 = load16(src + d0);
     const Vec16<T> x2 = load16(src + d0 + half);
-    const C* cr = cos_ + (int64_t)t * rope_n;
-    const C* sr = sin_ + (int64_t)t * rope_n;
+    const int64_t cs_row = ROWS ? (int64_t)b * Tn + t : (int64_t)t;
+    const C* cr = cos_ + cs_row * rope_n;
+    const C* sr = sin_ + cs_row * rope_n;
     Vec16<T> o1, o2;
 #pragma unroll
     for (int j = 0; j < VW; ++j) {
@@ -195,14 +218,18 @@ __device__ __forceinline__ void store_row_e4m3_scaled(uint8_t* row, uint8_t* sca
 // KT: the element type of the forward's k / v destination, T or uint8_t (an unscaled e4m3 cache: the
 // row rounded to T as for a T cache, then converted, so the launch equals RoPE + clamp + cast + copy).
 // KS: the uint8_t cache is the scaled one, one power-of-two scale byte per head row through `sd`.
-template <typename T, typename C, bool BWD, typename KT = T, bool KS = false>
+// ROWS (forward only): per-row positions, see RowsCap.  All items of a workgroup share the token, so a token
+// whose position is out of range skips its k / v heads as whole shuffle groups.
+template <typename T, typename C, bool BWD, typename KT = T, bool KS = false, bool ROWS = false>
 __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__ in0, const T* __restrict__ in1,
                                                            const T* __restrict__ in2, const C* __restrict__ cos_,
                                                            const C* __restrict__ sin_, T* __restrict__ out0,
                                                            KT* __restrict__ out1, KT* __restrict__ out2,
                                                            const int64_t* __restrict__ pos, KVDst st, int Tn, int nh,
                                                            int ng, int hs, int pair_shift,
-                                                           std::conditional_t<KS, ScaleDst, NoScale> sd) {
+                                                           std::conditional_t<KS, ScaleDst, NoScale> sd,
+                                                           std::conditional_t<ROWS, RowsCap, NoRows> rc) {
+  static_assert(!ROWS || !BWD, "per-row positions belong to the forward");
   // fwd: in0 = qkv, out0/1/2 = q/k/v (k/v through st); bwd: in0/1/2 = dq/dk/dv, out0 = dqkv
   constexpr int VW = 8;
   constexpr bool kE4M3 = !BWD && sizeof(KT) == 1;
@@ -210,8 +237,8 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
   const int t = row % Tn, b = row / Tn;
   const int heads = nh + 2 * ng, half = hs / 2;
   const int items = heads << pair_shift;
-  const C* cr = cos_ + (int64_t)t * hs;
-  const C* sr = sin_ + (int64_t)t * hs;
+  const C* cr = cos_ + (int64_t)(ROWS ? row : t) * hs;
+  const C* sr = sin_ + (int64_t)(ROWS ? row : t) * hs;
   for (int it = threadIdx.x; it < items; it += blockDim.x) {
     const int h = it >> pair_shift, d0 = (it & ((1 << pair_shift) - 1)) * VW;
     const T* src;
@@ -223,7 +250,13 @@ __global__ __launch_bounds__(256) void qkv_rope_row_kernel(const T* __restrict__
       if (h < nh) {
         dst = out0 + (((int64_t)b * nh + h) * Tn + t) * hs;
       } else {
-        const int64_t s = pos ? pos[t] : t;
+        int64_t s;
+        if constexpr (ROWS) {
+          s = pos[row];
+          if (s < 0 || s >= rc.S) continue;
+        } else {
+          s = pos ? pos[t] : t;
+        }
         if constexpr (kE4M3) {
           dst = nullptr;
           kv8 = h < nh + ng ? out1 + b * st.ksb + (h - nh) * st.ksg + s * st.kss
@@ -333,14 +366,14 @@ static int qkv_rope_fwd_launch(int dtype, int cdtype, const void* qkv, const voi
                     hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false>), dim3(B * Tn), dim3(256), 0, stream,
                                        (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
                                        (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, Tn, nh, ng, hs, sh,
-                                       NoScale{}));
+                                       NoScale{}, NoRows{}));
     return (int)hipGetLastError();
   }
   const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));
   LTA_DISPATCH_TC(dtype, cdtype,
                   hipLaunchKernelGGL((qkv_rope_fwd_kernel<T, C>), dim3(grid_for(total)), dim3(256), 0, stream,
                                      (const T*)qkv, (const C*)cos_, (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, B, Tn,
-                                     nh, ng, hs, rope_n));
+                                     nh, ng, hs, rope_n, NoRows{}));
   return (int)hipGetLastError();
 }
 
@@ -382,7 +415,7 @@ static int qkv_rope_e4m3_launch(int dtype, int cdtype, const void* qkv, const vo
                     hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, KS>), dim3(B * Tn), dim3(256), 0,
                                        stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
                                        (const C*)sin_, (T*)q, (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn,
-                                       nh, ng, hs, sh, sd));
+                                       nh, ng, hs, sh, sd, NoRows{}));
   return (int)hipGetLastError();
 }
 
@@ -406,6 +439,70 @@ LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s(int dtype, int cdtype, const void* qk
                                     stream, sd);
 }
 
+// The per-row entries (a ragged batch): cos / sin [B*Tn, rope_n], pos int64 [B*Tn], both indexed by b * Tn + t,
+// and the caches' capacity S; a token with a position outside [0, S) writes nothing but its q row.  Strides,
+// alignment and shape rules as for the shared-position entries.
+LTA_EXPORT int lta_qkv_rope_cache_fwd_rows(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
+                                           void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
+                                           int Tn, int nh, int ng, int hs, int rope_n, int S, hipStream_t stream) {
+  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
+  if (hs % 8 || rope_n % 16 || rope_n > hs || pos == nullptr || S < 0) return -2;
+  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  const RowsCap rc{S};
+  const int sh = row_pair_shift(dtype, hs, rope_n);
+  if (sh >= 0) {
+    LTA_DISPATCH_TC(dtype, cdtype,
+                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, T, false, true>), dim3(B * Tn), dim3(256), 0,
+                                       stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
+                                       (const C*)sin_, (T*)q, (T*)kc, (T*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs,
+                                       sh, NoScale{}, rc));
+    return (int)hipGetLastError();
+  }
+  const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));
+  LTA_DISPATCH_TC(dtype, cdtype,
+                  hipLaunchKernelGGL((qkv_rope_fwd_kernel<T, C, true>), dim3(grid_for(total)), dim3(256), 0, stream,
+                                     (const T*)qkv, (const C*)cos_, (const C*)sin_, (T*)q, (T*)kc, (T*)vc,
+                                     (const int64_t*)pos, st, B, Tn, nh, ng, hs, rope_n, rc));
+  return (int)hipGetLastError();
+}
+
+template <bool KS>
+static int qkv_rope_e4m3_rows_launch(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
+                                     void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
+                                     int Tn, int nh, int ng, int hs, int rope_n, int S, hipStream_t stream,
+                                     std::conditional_t<KS, ScaleDst, NoScale> sd) {
+  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
+  if (((uintptr_t)kc | (uintptr_t)vc) % 8 || pos == nullptr || S < 0) return -2;
+  const int sh = row_pair_shift(dtype, hs, rope_n);
+  if (sh < 0 || dtype == kF32) return -2;
+  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  LTA_DISPATCH_TC(dtype, cdtype,
+                  if constexpr (sizeof(T) == 2)
+                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, KS, true>), dim3(B * Tn), dim3(256),
+                                       0, stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
+                                       (const C*)sin_, (T*)q, (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn,
+                                       nh, ng, hs, sh, sd, RowsCap{S}));
+  return (int)hipGetLastError();
+}
+
+LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8_rows(int dtype, int cdtype, const void* qkv, const void* cos_,
+                                               const void* sin_, void* q, void* kc, void* vc, const void* pos,
+                                               const int64_t* strides, int B, int Tn, int nh, int ng, int hs,
+                                               int rope_n, int S, hipStream_t stream) {
+  return qkv_rope_e4m3_rows_launch<false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs,
+                                          rope_n, S, stream, NoScale{});
+}
+
+LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s_rows(int dtype, int cdtype, const void* qkv, const void* cos_,
+                                                const void* sin_, void* q, void* kc, void* vc, void* ksc, void* vsc,
+                                                const void* pos, const int64_t* strides, int B, int Tn, int nh, int ng,
+                                                int hs, int rope_n, int S, hipStream_t stream) {
+  if (row_pair_shift(dtype, hs, rope_n) > 6 || ksc == nullptr || vsc == nullptr) return -2;
+  const ScaleDst sd{(uint8_t*)ksc, (uint8_t*)vsc, strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
+  return qkv_rope_e4m3_rows_launch<true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs,
+                                         rope_n, S, stream, sd);
+}
+
 LTA_EXPORT int lta_qkv_rope_bwd(int dtype, int cdtype, const void* dq, const void* dk, const void* dv, const void* cos_,
                                 const void* sin_, void* dqkv, int B, int Tn, int nh, int ng, int hs, int rope_n,
                                 hipStream_t stream) {
@@ -416,7 +513,7 @@ LTA_EXPORT int lta_qkv_rope_bwd(int dtype, int cdtype, const void* dq, const voi
                     hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, true>), dim3(B * Tn), dim3(256), 0, stream,
                                        (const T*)dq, (const T*)dk, (const T*)dv, (const C*)cos_, (const C*)sin_,
                                        (T*)dqkv, (T*)nullptr, (T*)nullptr, (const int64_t*)nullptr, KVDst{0, 0, 0, 0, 0, 0},
-                                       Tn, nh, ng, hs, sh, NoScale{}));
+                                       Tn, nh, ng, hs, sh, NoScale{}, NoRows{}));
     return (int)hipGetLastError();
   }
   const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));

@@ -121,6 +121,74 @@ def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_siz
     return (q, *caches)
 
 
+# the per-row entries: the same pointers, and the caches' capacity S after rope_n
+for _entry, _scale_ptrs in (("lta_qkv_rope_cache_fwd_rows", 0), ("lta_qkv_rope_cache_fwd_kv8_rows", 0),
+                            ("lta_qkv_rope_cache_fwd_kv8s_rows", 2)):
+    register_signature(_entry, [c_int, c_int, *[c_void_p] * (8 + _scale_ptrs), *[c_int] * 7, c_void_p])
+
+
+def qkv_rope_cache_rows_supported(qkv, cos, sin, kc, vc, pos, n_query_groups: int, head_size: int,
+                                  rope_n: int | None = None, k_scale=None, v_scale=None) -> bool:
+    """What the per-row write takes: the caches of ``qkv_rope_cache_supported`` (or, with scale caches, of
+    ``qkv_rope_cache_scaled_supported``), one int64 position per token ``[B, T]`` and cos / sin ``[B, T, rope_n]``
+    gathered per token."""
+    if (k_scale is None) != (v_scale is None) or qkv.dim() != 3 or pos.dim() != 2:
+        return False
+    B, T, _ = qkv.shape
+    rn = head_size if rope_n is None else rope_n
+    if B == 0 or pos.dtype != torch.int64 or tuple(pos.shape) != (B, T) or pos.device != qkv.device:
+        return False
+    if head_size % 8 or rn % 16 or rn > head_size:
+        return False
+    if kc.dim() != 4 or vc.dim() != 4 or kc.shape[2] != vc.shape[2]:  # one capacity bounds every write
+        return False
+    if any(t.dim() != 3 or tuple(t.shape) != (B, T, rn) or not t.is_floating_point() for t in (cos, sin)):
+        return False
+    flat = _c(pos[0])  # the cache rules want T int64 positions; which ones does not matter to them
+    if k_scale is not None:
+        return qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, flat, n_query_groups, head_size, rn)
+    return qkv_rope_cache_supported(qkv, kc, vc, flat, n_query_groups, head_size, rn)
+
+
+def qkv_rope_cache_rows_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kc, vc, pos,
+                            k_scale=None, v_scale=None):
+    """``qkv_rope_cache_fwd`` for a ragged batch: ``pos`` int64 ``[B, T]`` and cos / sin ``[B, T, rope_n]`` hold
+    every token's own position and rotation; token (b, t) writes row ``pos[b, t]`` of sequence b's caches.  A
+    position outside ``[0, S)`` writes nothing (q is still returned for it).  Same bytes as the shared-position
+    write otherwise; returns (q, kc, vc) or (q, kc, vc, k_scale, v_scale)."""
+    if not qkv_rope_cache_rows_supported(qkv, cos, sin, kc, vc, pos, n_query_groups, head_size, rope_n, k_scale,
+                                         v_scale):
+        raise ValueError("qkv_rope_cache_rows_fwd: operands the per-row write does not take "
+                         "(see qkv_rope_cache_rows_supported)")
+    scales = () if k_scale is None else (k_scale, v_scale)
+    lib = require()
+    qkv = _c(qkv)
+    B, T, _ = qkv.shape
+    cos, sin, pos = _c(cos), _c(sin), _c(pos)
+    if cos.dtype != sin.dtype:
+        sin = sin.to(cos.dtype)
+    if cos.dtype not in (torch.float32, qkv.dtype):
+        cos, sin = cos.float(), sin.float()
+    q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
+    caches = (kc, vc, *scales)
+    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches for s in c.stride()[:3]))
+    entry = "lta_qkv_rope_cache_fwd" + ("_kv8s" if scales else "_kv8" if kc.dtype == torch.uint8 else "") + "_rows"
+    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), *map(ptr, caches), ptr(pos),
+                             st, B, T, n_head, n_query_groups, head_size, rope_n, kc.shape[2], stream_ptr(qkv.device))
+    check(rc, entry)
+    return (q, *caches)
+
+
+def qkv_rope_rows_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int):
+    """``qkv_rope_fwd`` with one rotation per token, cos / sin ``[B, T, rope_n]``: the per-row kernels writing fresh
+    k / v ``[B, ng, T, hs]`` at rows ``0 .. T-1``.  Returns (q, k, v)."""
+    B, T, _ = qkv.shape
+    k = torch.empty((B, n_query_groups, T, head_size), device=qkv.device, dtype=qkv.dtype)
+    v = torch.empty_like(k)
+    pos = torch.arange(T, device=qkv.device).expand(B, T).contiguous()
+    return qkv_rope_cache_rows_fwd(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, k, v, pos)
+
+
 def qkv_rope_bwd(dq, dk, dv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int):
     lib = require()
     dq, dk, dv = _c(dq), _c(dk), _c(dv)

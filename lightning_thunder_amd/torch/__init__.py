@@ -1752,6 +1752,7 @@ addcdiv_ = _inplace("addcdiv_", addcdiv)
 lerp_ = _inplace("lerp_", lerp)
 index_add_ = _inplace("index_add_", index_add)
 scatter_add_ = _inplace("scatter_add_", scatter_add)
+scatter_ = _inplace("scatter_", scatter)
 index_put_ = _inplace("index_put_", index_put)
 tril_ = _inplace("tril_", tril)
 triu_ = _inplace("triu_", triu)
