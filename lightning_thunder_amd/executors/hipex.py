@@ -913,29 +913,42 @@ def _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_
     return TensorProxy(like=qkv, shape=(B, n_head, T, head_size)), TensorProxy(like=kc), TensorProxy(like=vc)
 
 
-def _qkv_rope_cache_run(rope_args, caches, pos, supported, stored):
-    """The cache-writing RoPE over ``caches`` in operator order (kc, vc, then scale caches): the kernel
-    where ``supported`` takes the operands, else the program as the model spells it, with ``stored(t)``
-    the tensors k (or v) goes into its caches as."""
-    from ..ops.fused import qkv_rope_cache_fwd, qkv_rope_fwd
+def _qkv_rope_cache_run(rope_args, caches, pos, stored, rows=False):
+    """The cache-writing RoPE over ``caches`` in operator order (kc, vc, then scale caches): the kernel where its
+    ``*_supported`` takes the operands, else the program as the model spells it (RoPE, then one write per buffer),
+    with ``stored(t)`` the tensors k (or v) goes into its caches as.  ``rows``: ``pos`` is per token, int64 [B, T]."""
+    from ..ops import fused
+    from ..ops.kv_rows import write_rows
 
-    if supported(rope_args[0], *caches, pos, *rope_args[4:]):
-        return qkv_rope_cache_fwd(*rope_args, *caches[:2], pos, *caches[2:])
-    q, k, v = qkv_rope_fwd(*rope_args)
-    pos = pos if pos.dtype == torch.int64 else pos.long()  # index_copy_ takes int64 indices only
+    qkv, cos, sin, _, *shape = rope_args
+    if rows:
+        ok = fused.qkv_rope_cache_rows_supported(qkv, cos, sin, *caches[:2], pos, *shape, *caches[2:])
+        native, write = fused.qkv_rope_cache_rows_fwd, write_rows
+    else:
+        supported = fused.qkv_rope_cache_scaled_supported if len(caches) == 4 else fused.qkv_rope_cache_supported
+        ok, native = supported(qkv, *caches, pos, *shape), fused.qkv_rope_cache_fwd
+        write = lambda c, p, t: c.index_copy_(2, p if p.dtype == torch.int64 else p.long(), t)  # int64 indices only
+    if ok:
+        return native(*rope_args, *caches[:2], pos, *caches[2:])
+    q, k, v = _qkv_rope_impl(*rope_args)
     srcs = (t for pair in zip(stored(k), stored(v)) for t in pair)
-    return (q, *(c.index_copy_(2, pos, t) for c, t in zip(caches, srcs)))
+    return (q, *(write(c, pos, t) for c, t in zip(caches, srcs)))
+
+
+def _unscaled_stored(op: str, kc, vc):
+    """``stored`` of ``_qkv_rope_cache_run`` for unscaled caches: k / v as they are, or their e4m3 bytes for uint8
+    caches (models/litgpt.py KVCache); operator ``op`` refuses one of each."""
+    from ..ops.kv8 import e4m3_bytes
+
+    kv8 = kc.dtype == torch.uint8
+    if kv8 != (vc.dtype == torch.uint8):
+        raise ValueError(f"{op}: one of the two caches is uint8 (e4m3), the other is not")
+    return (lambda t: (e4m3_bytes(t),)) if kv8 else (lambda t: (t,))
 
 
 def _qkv_rope_cache_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
-    from ..ops.fused import qkv_rope_cache_supported
-    from ..ops.kv8 import e4m3_bytes
-
-    kv8 = kc.dtype == torch.uint8  # unscaled e4m3 caches (models/litgpt.py KVCache)
-    if kv8 != (vc.dtype == torch.uint8):
-        raise ValueError("hip_qkv_rope_cache: one of the two caches is uint8 (e4m3), the other is not")
     return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n), (kc, vc), pos,
-                               qkv_rope_cache_supported, (lambda t: (e4m3_bytes(t),)) if kv8 else (lambda t: (t,)))
+                               _unscaled_stored("hip_qkv_rope_cache", kc, vc))
 
 
 hip_qkv_rope_cache = ex.register_operator("hip_qkv_rope_cache", meta=_qkv_rope_cache_meta, fn=_qkv_rope_cache_impl,
@@ -951,11 +964,10 @@ def _qkv_rope_cache_s8_meta(qkv, cos, sin, n_head, n_query_groups, head_size, ro
 
 
 def _qkv_rope_cache_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, k_scale, v_scale, pos):
-    from ..ops.fused import qkv_rope_cache_scaled_supported
     from ..ops.kv8 import quantise_rows
 
     return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n),
-                               (kc, vc, k_scale, v_scale), pos, qkv_rope_cache_scaled_supported, quantise_rows)
+                               (kc, vc, k_scale, v_scale), pos, quantise_rows)
 
 
 hip_qkv_rope_cache_s8 = ex.register_operator("hip_qkv_rope_cache_s8", meta=_qkv_rope_cache_s8_meta,
@@ -965,37 +977,17 @@ hip_qkv_rope_cache_s8.written_args = (7, 8, 9, 10)  # kc, vc, k_scale, v_scale
 
 # Ragged batches: one int64 position per (sequence, token), ``pos`` [B, T], with cos / sin [B, T, rope_n] gathered per
 # token (ops/kv_rows.py).  The operators mirror the two above, over the per-row entries of csrc/rope.hip.
-def _qkv_rope_cache_rows_run(rope_args, caches, pos, stored):
-    """As ``_qkv_rope_cache_run`` for per-row positions: the kernel where ``qkv_rope_cache_rows_supported`` takes the
-    operands, else the program as the model spells it (RoPE, then one row write per buffer)."""
-    from ..ops.fused import qkv_rope_cache_rows_fwd, qkv_rope_cache_rows_supported
-    from ..ops.kv_rows import write_rows
-
-    qkv, cos, sin, _, n_query_groups, head_size, rope_n = rope_args
-    if qkv_rope_cache_rows_supported(qkv, cos, sin, caches[0], caches[1], pos, n_query_groups, head_size, rope_n,
-                                     *caches[2:]):
-        return qkv_rope_cache_rows_fwd(*rope_args, *caches[:2], pos, *caches[2:])
-    q, k, v = _qkv_rope_impl(*rope_args)
-    srcs = (t for pair in zip(stored(k), stored(v)) for t in pair)
-    return (q, *(write_rows(c, pos, t) for c, t in zip(caches, srcs)))
-
-
 def _qkv_rope_cache_rows_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, pos):
-    from ..ops.kv8 import e4m3_bytes
-
-    kv8 = kc.dtype == torch.uint8
-    if kv8 != (vc.dtype == torch.uint8):
-        raise ValueError("hip_qkv_rope_cache_rows: one of the two caches is uint8 (e4m3), the other is not")
-    return _qkv_rope_cache_rows_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n), (kc, vc), pos,
-                                    (lambda t: (e4m3_bytes(t),)) if kv8 else (lambda t: (t,)))
+    return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n), (kc, vc), pos,
+                               _unscaled_stored("hip_qkv_rope_cache_rows", kc, vc), rows=True)
 
 
 def _qkv_rope_cache_rows_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kc, vc, k_scale, v_scale,
                                  pos):
     from ..ops.kv8 import quantise_rows
 
-    return _qkv_rope_cache_rows_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n),
-                                    (kc, vc, k_scale, v_scale), pos, quantise_rows)
+    return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n),
+                               (kc, vc, k_scale, v_scale), pos, quantise_rows, rows=True)
 
 
 hip_qkv_rope_cache_rows = ex.register_operator("hip_qkv_rope_cache_rows", meta=_qkv_rope_cache_meta,
@@ -2054,22 +2046,23 @@ def _decode_attn_kv8_meta(q, k8, v8, mask, causal, scale):
     return TensorProxy(like=q)
 
 
-def _decode_attn_e4m3_run(q, caches, mask, causal, scale, supported, kernel, dequantise):
-    """Decode attention over e4m3 ``caches`` in operator order (k8, v8, then scale caches): ``kernel``
-    where ``supported`` takes the operands, else (a head dim the e4m3 kernel does not take) the program
-    as the model spells it, ``dequantise(<a cache's operands>, dtype)`` and the 16-bit kernel."""
-    from ..ops.attention import decode_attn
-
-    if supported(q, *caches):
-        return kernel(q, *caches, mask, causal, scale)
-    return decode_attn(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), mask, causal, scale)
+def _decode_attn_e4m3_run(q, caches, selector, scale, supported, kernel, dequantise):
+    """Decode attention over e4m3 ``caches`` in operator order (k8, v8, then scale caches), for keys chosen by
+    ``selector`` = (mask, causal) or (pos,): ``kernel`` where ``supported`` takes the operands, else (more query
+    rows or a head dim the e4m3 kernel does not take) the program as the model spells it,
+    ``dequantise(<a cache's operands>, dtype)`` and the 16-bit operator."""
+    by_pos = len(selector) == 1
+    if supported(q, *caches, *(selector if by_pos else ())):
+        return kernel(q, *caches, *selector, scale)
+    plain = _decode_attn_pos_impl if by_pos else _decode_attn_impl
+    return plain(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), *selector, scale)
 
 
 def _decode_attn_kv8_impl(q, k8, v8, mask, causal, scale):
     from ..ops.attention import decode_attn_kv8, decode_attn_kv8_supported
     from ..ops.kv8 import e4m3_values
 
-    return _decode_attn_e4m3_run(q, (k8, v8), mask, causal, scale, decode_attn_kv8_supported, decode_attn_kv8,
+    return _decode_attn_e4m3_run(q, (k8, v8), (mask, causal), scale, decode_attn_kv8_supported, decode_attn_kv8,
                                  e4m3_values)
 
 
@@ -2084,7 +2077,7 @@ def _decode_attn_kv8s_impl(q, k8, v8, k_scale, v_scale, mask, causal, scale):
     from ..ops.attention import decode_attn_kv8s, decode_attn_kv8s_supported
     from ..ops.kv8 import dequantise_rows
 
-    return _decode_attn_e4m3_run(q, (k8, v8, k_scale, v_scale), mask, causal, scale, decode_attn_kv8s_supported,
+    return _decode_attn_e4m3_run(q, (k8, v8, k_scale, v_scale), (mask, causal), scale, decode_attn_kv8s_supported,
                                  decode_attn_kv8s, dequantise_rows)
 
 
@@ -2106,28 +2099,20 @@ def _decode_attn_pos_impl(q, k, v, pos, scale):
     return decode_attn(q, k, v, position_mask(pos, k.shape[2]), False, scale)
 
 
-def _decode_attn_e4m3_pos_run(q, caches, pos, scale, supported, kernel, dequantise):
-    """As ``_decode_attn_e4m3_run``: ``kernel`` where ``supported`` takes the operands, else the program as the model
-    spells it, ``dequantise`` and the 16-bit position operator."""
-    if supported(q, *caches, pos):
-        return kernel(q, *caches, pos, scale)
-    return _decode_attn_pos_impl(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), pos, scale)
-
-
 def _decode_attn_kv8_pos_impl(q, k8, v8, pos, scale):
     from ..ops.attention import decode_attn_kv8_pos, decode_attn_kv8_pos_supported
     from ..ops.kv8 import e4m3_values
 
-    return _decode_attn_e4m3_pos_run(q, (k8, v8), pos, scale, decode_attn_kv8_pos_supported, decode_attn_kv8_pos,
-                                     e4m3_values)
+    return _decode_attn_e4m3_run(q, (k8, v8), (pos,), scale, decode_attn_kv8_pos_supported, decode_attn_kv8_pos,
+                                 e4m3_values)
 
 
 def _decode_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale):
     from ..ops.attention import decode_attn_kv8s_pos, decode_attn_kv8s_pos_supported
     from ..ops.kv8 import dequantise_rows
 
-    return _decode_attn_e4m3_pos_run(q, (k8, v8, k_scale, v_scale), pos, scale, decode_attn_kv8s_pos_supported,
-                                     decode_attn_kv8s_pos, dequantise_rows)
+    return _decode_attn_e4m3_run(q, (k8, v8, k_scale, v_scale), (pos,), scale, decode_attn_kv8s_pos_supported,
+                                 decode_attn_kv8s_pos, dequantise_rows)
 
 
 hip_decode_attn_pos = ex.register_operator("hip_decode_attn_pos", meta=_decode_attn_pos_meta, fn=_decode_attn_pos_impl)

@@ -246,32 +246,12 @@ class KVCache(nn.Module):
                                      persistent=False)
 
     def forward(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
-        if input_pos.dim() == 2:
-            return self._forward_rows(input_pos, k, v)
-        if self.scale is not None:
-            k8, ks = kv8_quantise_rows(k)
-            v8, vs = kv8_quantise_rows(v)
-            k_all = self.k.index_copy_(2, input_pos, k8)
-            v_all = self.v.index_copy_(2, input_pos, v8)
-            ks_all = self.k_scale.index_copy_(2, input_pos, ks)
-            vs_all = self.v_scale.index_copy_(2, input_pos, vs)
-            return kv8_dequantise_rows(k_all, ks_all, k.dtype), kv8_dequantise_rows(v_all, vs_all, v.dtype)
-        if self.k.dtype == torch.uint8:
-            f8 = torch.float8_e4m3fn
-            k8 = k.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
-            v8 = v.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
-            k_all = self.k.index_copy_(2, input_pos, k8)
-            v_all = self.v.index_copy_(2, input_pos, v8)
-            return k_all.view(f8).to(k.dtype), v_all.view(f8).to(v.dtype)
-        k_all = self.k.index_copy_(2, input_pos, k.to(self.k.dtype))
-        v_all = self.v.index_copy_(2, input_pos, v.to(self.v.dtype))
-        return k_all, v_all
-
-    def _forward_rows(self, input_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
-        """``forward`` with per-sequence positions: the same formats, each buffer written with one O(tokens)
-        ``scatter_`` along the key dim (LitGPT's spelling of the batched write)."""
-        def put(cache, src):
-            return cache.scatter_(2, input_pos[:, None, :, None].expand_as(src), src)
+        if input_pos.dim() == 2:  # per-sequence positions: one O(tokens) ``scatter_`` along the key dim per buffer
+            def put(cache, src):  # (LitGPT's spelling of the batched write)
+                return cache.scatter_(2, input_pos[:, None, :, None].expand_as(src), src)
+        else:
+            def put(cache, src):
+                return cache.index_copy_(2, input_pos, src)
 
         if self.scale is not None:
             k8, ks = kv8_quantise_rows(k)

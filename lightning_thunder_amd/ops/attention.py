@@ -379,10 +379,12 @@ import ctypes  # noqa: E402
 from ._lib import c_int64  # noqa: E402
 from .kv8 import scale_caches_of  # noqa: E402
 
-# the decode entries: pointers q, k, v, <scale caches>, mask, o, ws_acc, ws_ml
+# the decode entries: pointers q, k, v, <scale caches>, mask (or pos), o, ws_acc, ws_ml, then the sizes and strides; the
+# mask entries go on with chunk, nsplit, causal, the position entries with nsplit alone
 for _entry, _scale_ptrs in (("lta_decode_attn", 0), ("lta_decode_attn_kv8", 0), ("lta_decode_attn_kv8s", 2)):
-    register_signature(_entry, [c_int, *[c_void_p] * (7 + _scale_ptrs), *[c_int] * 6, c_void_p, c_int, c_int, c_int,
-                                c_float, c_int, c_void_p])
+    _head = [c_int, *[c_void_p] * (7 + _scale_ptrs), *[c_int] * 6, c_void_p]
+    register_signature(_entry, [*_head, c_int, c_int, c_int, c_float, c_int, c_void_p])
+    register_signature(_entry + "_pos", [*_head, c_int, c_float, c_int, c_void_p])
 
 DECODE_MAX_QUERIES = 16
 
@@ -400,18 +402,18 @@ def decode_launch_shape(rows: int, S: int):
     return wsplit, nsplit, chunk
 
 
-def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None, scales=None):
-    """One launch of ``entry``; ``scales`` = (k_scale, v_scale) for the scaled-e4m3 entry, whose argument
-    list carries the two pointers after v and their (b, h, s) strides after the mask's."""
+def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: bool = False, pos=None, scales=()):
+    """One launch of ``entry``: a mask entry with (``mask``, ``causal``), a position entry with ``pos``.  ``scales`` =
+    (k_scale, v_scale) for the scaled-e4m3 entries, whose argument list carries the two pointers after v.  The
+    stride record is q, k, v (b, h, t each), then the selector's (mask b, h, t, s or pos b, t), then the scales'.
+
+    The grid comes from the capacity S in both modes (``decode_launch_shape``): positions stay on the device, so a
+    hipGraph replays the launch while they advance; the kernel splits each row's live range over the ``nsplit``
+    workgroups itself."""
     lib = require()
     B, Hq, T, D = q.shape
     Hkv, S = k.shape[1], k.shape[2]
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
-    if mask is not None:
-        mask = torch.broadcast_to(mask, (B, Hq, T, S))
-        ms = mask.stride()
-    else:
-        ms = (0, 0, 0, 0)
     rows = B * Hq * T
     wsplit, nsplit, chunk = decode_launch_shape(rows, S)
     o = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
@@ -419,30 +421,48 @@ def _decode_launch(entry: str, q, k, v, mask, causal: bool, scale: float | None,
     if nsplit > 1:
         ws_acc = torch.empty((nsplit, rows, D), device=q.device, dtype=torch.float32)
         ws_ml = torch.empty((nsplit, rows, 2), device=q.device, dtype=torch.float32)
-    extra = () if scales is None else (*scales[0].stride()[:3], *scales[1].stride()[:3])
-    st = (ctypes.c_int64 * (13 + len(extra)))(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-                                              k.stride(2), v.stride(0), v.stride(1), v.stride(2), *ms, *extra)
-    mptr = None if mask is None else mask.data_ptr()
-    sptrs = () if scales is None else (ptr(scales[0]), ptr(scales[1]))
-    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *sptrs, mptr, ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq, Hkv,
-                             T, S, D, ctypes.cast(st, ctypes.c_void_p), chunk, nsplit, int(causal), float(sc),
+    if pos is not None:
+        sel, sel_st, split = pos, pos.stride(), (nsplit,)
+    else:
+        sel = mask if mask is None else torch.broadcast_to(mask, (B, Hq, T, S))
+        sel_st, split = (0, 0, 0, 0) if mask is None else sel.stride(), (chunk, nsplit, int(causal))
+    st = (*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *sel_st, *(s for c in scales for s in c.stride()[:3]))
+    st = (ctypes.c_int64 * len(st))(*st)
+    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *map(ptr, scales), ptr(sel), ptr(o), ptr(ws_acc),
+                             ptr(ws_ml), B, Hq, Hkv, T, S, D, ctypes.cast(st, ctypes.c_void_p), *split, float(sc),
                              int(wsplit), stream_ptr(q.device))
     check(rc, entry)
     return o
 
 
+def _refusal(fn: str, **operands) -> ValueError:
+    """The error of a wrapper whose ``*_supported`` said no: ``fn`` and every operand's dtype and shape."""
+    return ValueError(f"{fn}: unsupported operands " + ", ".join(
+        f"{name} {None if t is None else (t.dtype, tuple(t.shape))}" for name, t in operands.items()))
+
+
+def _cache_operands_ok(q, k, v, cache_dtype) -> bool:
+    """The shape rule of every kernel that checks its operands: 16-bit q [B, Hq, T, D] with D 64 / 128 and at most
+    DECODE_MAX_QUERIES rows, k / v [B, Hkv, S, D] of ``cache_dtype`` with Hkv dividing Hq."""
+    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
+            and q.shape[2] <= DECODE_MAX_QUERIES and k.dtype == cache_dtype and v.dtype == cache_dtype
+            and k.dim() == 4 and k.shape == v.shape and k.shape[-1] == q.shape[-1] and k.shape[0] == q.shape[0]
+            and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0)
+
+
+def _e4m3_in_place(q, k8, v8):
+    return _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
+
+
 def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = None):
     """q [B, Hq, T, D] (T <= 16), k/v [B, Hkv, S, D], mask bool broadcastable to [B, Hq, T, S] -> [B, Hq, T, D]."""
     q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
-    return _decode_launch("lta_decode_attn", q, k, v, mask, causal, scale)
+    return _decode_launch("lta_decode_attn", q, k, v, scale, mask, causal)
 
 
 def decode_attn_kv8_supported(q, k8, v8) -> bool:
     """What the e4m3-cache decode kernel takes: 16-bit q of head dim 64 / 128, uint8 k / v."""
-    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
-            and q.shape[2] <= DECODE_MAX_QUERIES and k8.dtype == torch.uint8 and v8.dtype == torch.uint8
-            and k8.dim() == 4 and k8.shape == v8.shape and k8.shape[-1] == q.shape[-1] and k8.shape[0] == q.shape[0]
-            and k8.shape[1] > 0 and q.shape[1] % k8.shape[1] == 0)
+    return _cache_operands_ok(q, k8, v8, torch.uint8)
 
 
 def _rows8_in_place(t):
@@ -457,10 +477,8 @@ def decode_attn_kv8(q, k8, v8, mask=None, causal: bool = False, scale: float | N
     """``decode_attn`` over an unscaled OCP e4m3 cache: k8 / v8 uint8 [B, Hkv, S, D] (the bytes of
     ``float8_e4m3fn``), unpacked in the kernel; q and the result are bf16 / fp16."""
     if not decode_attn_kv8_supported(q, k8, v8):
-        raise ValueError(f"decode_attn_kv8: unsupported operands q {q.dtype} {tuple(q.shape)}, "
-                         f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}")
-    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
-    return _decode_launch("lta_decode_attn_kv8", q, k8, v8, mask, causal, scale)
+        raise _refusal("decode_attn_kv8", q=q, k=k8, v=v8)
+    return _decode_launch("lta_decode_attn_kv8", *_e4m3_in_place(q, k8, v8), scale, mask, causal)
 
 
 def decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale) -> bool:
@@ -475,23 +493,14 @@ def decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask=None, causal: bool = Fals
     ``dequantise_rows(k8, k_scale, q.dtype)`` / ``dequantise_rows(v8, v_scale, q.dtype)`` bit for bit (fp32
     subnormal or overflowing partial sums aside); the scales are read in place."""
     if not decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale):
-        raise ValueError(f"decode_attn_kv8s: unsupported operands q {q.dtype} {tuple(q.shape)}, "
-                         f"k {k8.dtype} {tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, scales "
-                         f"{None if k_scale is None else (k_scale.dtype, tuple(k_scale.shape))} / "
-                         f"{None if v_scale is None else (v_scale.dtype, tuple(v_scale.shape))}")
-    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
-    return _decode_launch("lta_decode_attn_kv8s", q, k8, v8, mask, causal, scale, scales=(k_scale, v_scale))
+        raise _refusal("decode_attn_kv8s", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale)
+    return _decode_launch("lta_decode_attn_kv8s", *_e4m3_in_place(q, k8, v8), scale, mask, causal,
+                          scales=(k_scale, v_scale))
 
 
 # ------------------------------------------------------------------------------------------------
 # Position mode of the decode kernels (ragged batches): every row's key count from pos[b, t], no mask
 # ------------------------------------------------------------------------------------------------
-# the position entries: pointers q, k, v, <scale caches>, pos, o, ws_acc, ws_ml
-for _entry, _scale_ptrs in (("lta_decode_attn_pos", 0), ("lta_decode_attn_kv8_pos", 0), ("lta_decode_attn_kv8s_pos", 2)):
-    register_signature(_entry, [c_int, *[c_void_p] * (7 + _scale_ptrs), *[c_int] * 6, c_void_p, c_int, c_float, c_int,
-                                c_void_p])
-
-
 def _pos_ok(q, k, pos) -> bool:
     """int64 positions [B, T] (any strides) on q's device, at most DECODE_MAX_QUERIES query rows."""
     return (pos is not None and pos.dtype == torch.int64 and pos.dim() == 2 and q.dim() == 4 and k.dim() == 4
@@ -502,9 +511,7 @@ def _pos_ok(q, k, pos) -> bool:
 def decode_attn_pos_supported(q, k, v, pos) -> bool:
     """What the 16-bit position kernel takes: bf16 / fp16 q, k, v of one dtype and head dim 64 / 128, GQA
     head counts, int64 ``pos`` [B, T] with T <= 16."""
-    return (_pos_ok(q, k, pos) and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype
-            and v.dtype == q.dtype and q.shape[-1] in (64, 128) and k.shape == v.shape and k.shape[-1] == q.shape[-1]
-            and k.shape[0] == q.shape[0] and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0)
+    return _pos_ok(q, k, pos) and _cache_operands_ok(q, k, v, q.dtype)
 
 
 def decode_attn_kv8_pos_supported(q, k8, v8, pos) -> bool:
@@ -515,62 +522,28 @@ def decode_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos) -> bool:
     return _pos_ok(q, k8, pos) and decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale)
 
 
-def _decode_pos_launch(entry: str, q, k, v, pos, scale: float | None, scales=None):
-    """One launch of a position entry.  The grid comes from the capacity S as for the mask entries
-    (``decode_launch_shape``): the positions stay on the device, so a hipGraph replays the launch while they
-    advance; the kernel splits each row's live range over the ``nsplit`` workgroups itself."""
-    lib = require()
-    B, Hq, T, D = q.shape
-    Hkv, S = k.shape[1], k.shape[2]
-    sc = scale if scale is not None else 1.0 / math.sqrt(D)
-    rows = B * Hq * T
-    wsplit, nsplit, _ = decode_launch_shape(rows, S)
-    o = torch.empty((B, Hq, T, D), device=q.device, dtype=q.dtype)
-    ws_acc = ws_ml = None
-    if nsplit > 1:
-        ws_acc = torch.empty((nsplit, rows, D), device=q.device, dtype=torch.float32)
-        ws_ml = torch.empty((nsplit, rows, 2), device=q.device, dtype=torch.float32)
-    extra = () if scales is None else (*scales[0].stride()[:3], *scales[1].stride()[:3])
-    st = (ctypes.c_int64 * (11 + len(extra)))(q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-                                              k.stride(2), v.stride(0), v.stride(1), v.stride(2), pos.stride(0),
-                                              pos.stride(1), *extra)
-    sptrs = () if scales is None else (ptr(scales[0]), ptr(scales[1]))
-    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *sptrs, ptr(pos), ptr(o), ptr(ws_acc), ptr(ws_ml), B, Hq,
-                             Hkv, T, S, D, ctypes.cast(st, ctypes.c_void_p), nsplit, float(sc), int(wsplit),
-                             stream_ptr(q.device))
-    check(rc, entry)
-    return o
-
-
 def decode_attn_pos(q, k, v, pos, scale: float | None = None):
     """Decode attention of a ragged batch: q [B, Hq, T, D] (T <= 16), k / v [B, Hkv, S, D], ``pos`` int64
     [B, T].  Row (b, hq, t) attends keys ``0 .. n-1`` with ``n = clamp(pos[b, t] + 1, 0, S)``: what
     ``decode_attn`` computes under the mask ``arange(S) <= pos[b, t]``, without the mask tensor and with the
     row's live keys split over all of its workgroups.  ``n = 0`` gives a NaN row, like a fully masked one."""
     if not decode_attn_pos_supported(q, k, v, pos):
-        raise ValueError(f"decode_attn_pos: unsupported operands q {q.dtype} {tuple(q.shape)}, k {k.dtype} "
-                         f"{tuple(k.shape)}, v {v.dtype} {tuple(v.shape)}, pos "
-                         f"{None if pos is None else (pos.dtype, tuple(pos.shape))}")
+        raise _refusal("decode_attn_pos", q=q, k=k, v=v, pos=pos)
     q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
-    return _decode_pos_launch("lta_decode_attn_pos", q, k, v, pos, scale)
+    return _decode_launch("lta_decode_attn_pos", q, k, v, scale, pos=pos)
 
 
 def decode_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None):
     """``decode_attn_pos`` over an unscaled e4m3 cache (the operands of ``decode_attn_kv8``)."""
     if not decode_attn_kv8_pos_supported(q, k8, v8, pos):
-        raise ValueError(f"decode_attn_kv8_pos: unsupported operands q {q.dtype} {tuple(q.shape)}, k {k8.dtype} "
-                         f"{tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, pos "
-                         f"{None if pos is None else (pos.dtype, tuple(pos.shape))}")
-    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
-    return _decode_pos_launch("lta_decode_attn_kv8_pos", q, k8, v8, pos, scale)
+        raise _refusal("decode_attn_kv8_pos", q=q, k=k8, v=v8, pos=pos)
+    return _decode_launch("lta_decode_attn_kv8_pos", *_e4m3_in_place(q, k8, v8), scale, pos=pos)
 
 
 def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None):
     """``decode_attn_pos`` over the scaled e4m3 cache (the operands of ``decode_attn_kv8s``): equals
     ``decode_attn_pos`` over the dequantised cache bit for bit, with that kernel's exclusions."""
     if not decode_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
-        raise ValueError(f"decode_attn_kv8s_pos: unsupported operands q {q.dtype} {tuple(q.shape)}, k {k8.dtype} "
-                         f"{tuple(k8.shape)}, v {v8.dtype} {tuple(v8.shape)}, pos "
-                         f"{None if pos is None else (pos.dtype, tuple(pos.shape))}")
-    q, k8, v8 = _rows_in_place(q), _rows8_in_place(k8), _rows8_in_place(v8)
-    return _decode_pos_launch("lta_decode_attn_kv8s_pos", q, k8, v8, pos, scale, scales=(k_scale, v_scale))
+        raise _refusal("decode_attn_kv8s_pos", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos)
+    return _decode_launch("lta_decode_attn_kv8s_pos", *_e4m3_in_place(q, k8, v8), scale, pos=pos,
+                          scales=(k_scale, v_scale))

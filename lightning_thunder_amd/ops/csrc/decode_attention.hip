@@ -341,18 +341,47 @@ bool e4m3_cache_ok(const void* k, const void* v, const int64_t* strides) {
   return (((uintptr_t)k | (uintptr_t)v) % 16) == 0;
 }
 
+// The host side of every entry: the checks, then the kernels' records out of `strides`, which holds (elements;
+// 0 for broadcast dims; head dim contiguous)
+//   q b,h,t | k b,h,s | v b,h,s | the selector's | with KS: k scale b,h,s | v scale b,h,s (bytes),
+// where the selector `sel` is the bool mask (strides b,h,t,s; may be null) or, with POS, the int64 positions
+// [B, Tq] (strides b,t; see RowPos).  KV = void: the cache holds q's type; uint8_t: e4m3.
+template <typename KV, bool KS, bool POS>
+int decode_entry(int dtype, const void* q, const void* k, const void* v, const void* k_scale, const void* v_scale,
+                 const void* sel, void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                 const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit, void* stream) {
+  constexpr int kSel = POS ? 2 : 4;  // strides of the selector; the scales' follow them
+  if (!sizes_ok(Hq, Hkv, POS ? 64 : chunk, nsplit)) return (int)hipErrorInvalidValue;  // POS: no chunk to check
+  if (nsplit > 1 && (ws_acc == nullptr || ws_ml == nullptr)) return (int)hipErrorInvalidValue;
+  if constexpr (std::is_same_v<KV, uint8_t>)
+    if (!e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
+  int64_t st[13] = {};  // the kernels' q, k, v and mask strides; without a mask its four stay 0
+  for (int i = 0; i < (POS ? 9 : 13); ++i) st[i] = strides[i];
+  std::conditional_t<KS, KVScales, NoScales> sc{};
+  if constexpr (KS) {
+    if (k_scale == nullptr || v_scale == nullptr) return (int)hipErrorInvalidValue;
+    const int64_t* ss = strides + 9 + kSel;
+    sc = KVScales{(const uint8_t*)k_scale, (const uint8_t*)v_scale, ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]};
+  }
+  std::conditional_t<POS, RowPos, NoPos> rp{};
+  if constexpr (POS) {
+    if (sel == nullptr || S < 0) return (int)hipErrorInvalidValue;
+    rp = RowPos{(const int64_t*)sel, strides[9], strides[10]};
+  }
+  return dispatch<KV, KS, POS>(dtype, D, q, k, v, POS ? (const void*)nullptr : sel, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
+                               (const int64_t*)st, chunk, nsplit, causal, scale, wsplit, (hipStream_t)stream, sc, rp);
+}
+
 }  // namespace
 }  // namespace lta
 
-// strides (elements): q b,h,t | k b,h,s | v b,h,s | mask b,h,t,s (0 for broadcast dims); head dim contiguous.
+// The mask entries; `strides` as decode_entry has them.
 LTA_EXPORT int lta_decode_attn(int dtype, const void* q, const void* k, const void* v, const void* mask, void* o,
                                void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
                                const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit,
                                void* stream) {
-  using namespace lta;
-  if (!sizes_ok(Hq, Hkv, chunk, nsplit)) return (int)hipErrorInvalidValue;
-  return dispatch<void>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal,
-                        scale, wsplit, (hipStream_t)stream);
+  return lta::decode_entry<void, false, false>(dtype, q, k, v, nullptr, nullptr, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq,
+                                               S, D, strides, chunk, nsplit, causal, scale, wsplit, stream);
 }
 
 // The same launch over an unscaled OCP e4m3 cache: k / v are uint8 [B, Hkv, S, D] (strides in elements
@@ -361,74 +390,41 @@ LTA_EXPORT int lta_decode_attn_kv8(int dtype, const void* q, const void* k, cons
                                    void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
                                    const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit,
                                    void* stream) {
-  using namespace lta;
-  if (!sizes_ok(Hq, Hkv, chunk, nsplit) || !e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
-  return dispatch<uint8_t>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit, causal,
-                           scale, wsplit, (hipStream_t)stream);
+  return lta::decode_entry<uint8_t, false, false>(dtype, q, k, v, nullptr, nullptr, mask, o, ws_acc, ws_ml, B, Hq, Hkv,
+                                                  Tq, S, D, strides, chunk, nsplit, causal, scale, wsplit, stream);
 }
 
 // The same launch over the scaled e4m3 cache of ops/kv8.py: k / v as for lta_decode_attn_kv8, k_scale / v_scale
-// uint8 [B, Hkv, S, 1] holding e + 127 per row; strides[13..18] are theirs (bytes): k scale b,h,s | v scale b,h,s.
+// uint8 [B, Hkv, S, 1] holding e + 127 per row.
 LTA_EXPORT int lta_decode_attn_kv8s(int dtype, const void* q, const void* k, const void* v, const void* k_scale,
                                     const void* v_scale, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
                                     int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int chunk, int nsplit,
                                     int causal, float scale, int wsplit, void* stream) {
-  using namespace lta;
-  if (!sizes_ok(Hq, Hkv, chunk, nsplit) || !e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
-  if (k_scale == nullptr || v_scale == nullptr) return (int)hipErrorInvalidValue;
-  const KVScales sc{(const uint8_t*)k_scale, (const uint8_t*)v_scale, strides[13], strides[14], strides[15],
-                    strides[16], strides[17], strides[18]};
-  return dispatch<uint8_t, true>(dtype, D, q, k, v, mask, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, strides, chunk, nsplit,
-                                 causal, scale, wsplit, (hipStream_t)stream, sc);
+  return lta::decode_entry<uint8_t, true, false>(dtype, q, k, v, k_scale, v_scale, mask, o, ws_acc, ws_ml, B, Hq, Hkv,
+                                                 Tq, S, D, strides, chunk, nsplit, causal, scale, wsplit, stream);
 }
 
 // The position entries: no mask and no causal flag; `pos` int64 [B, Tq] gives every row its key count (see
-// RowPos).  strides: q b,h,t | k b,h,s | v b,h,s | pos b,t (| k scale b,h,s | v scale b,h,s for the scaled cache).
-// `nsplit` is the host's split count for the capacity S; the kernel derives each row's own chunk from it.
-namespace lta {
-namespace {
-
-template <typename KV, bool KS>
-int launch_pos(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o, void* ws_acc,
-               void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int nsplit,
-               float scale, int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc) {
-  if (!sizes_ok(Hq, Hkv, 64, nsplit) || pos == nullptr || S < 0) return (int)hipErrorInvalidValue;
-  if (nsplit > 1 && (ws_acc == nullptr || ws_ml == nullptr)) return (int)hipErrorInvalidValue;
-  int64_t st[13] = {};  // the mask's four strides stay 0
-  for (int i = 0; i < 9; ++i) st[i] = strides[i];
-  const RowPos rp{(const int64_t*)pos, strides[9], strides[10]};
-  return dispatch<KV, KS, true>(dtype, D, q, k, v, (const void*)nullptr, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
-                                (const int64_t*)st, 0, nsplit, 0, scale, wsplit, stream, sc, rp);
-}
-
-}  // namespace
-}  // namespace lta
-
+// RowPos).  `nsplit` is the host's split count for the capacity S; the kernel derives each row's own chunk from
+// it and reads neither `chunk` nor `causal`, which go on as 0.
 LTA_EXPORT int lta_decode_attn_pos(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o,
                                    void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
                                    const int64_t* strides, int nsplit, float scale, int wsplit, void* stream) {
-  using namespace lta;
-  return launch_pos<void, false>(dtype, q, k, v, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, D, strides, nsplit, scale,
-                                 wsplit, (hipStream_t)stream, NoScales{});
+  return lta::decode_entry<void, false, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
+                                              D, strides, 0, nsplit, 0, scale, wsplit, stream);
 }
 
 LTA_EXPORT int lta_decode_attn_kv8_pos(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o,
                                        void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
                                        const int64_t* strides, int nsplit, float scale, int wsplit, void* stream) {
-  using namespace lta;
-  if (!e4m3_cache_ok(k, v, strides)) return (int)hipErrorInvalidValue;
-  return launch_pos<uint8_t, false>(dtype, q, k, v, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, D, strides, nsplit,
-                                    scale, wsplit, (hipStream_t)stream, NoScales{});
+  return lta::decode_entry<uint8_t, false, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq,
+                                                 S, D, strides, 0, nsplit, 0, scale, wsplit, stream);
 }
 
 LTA_EXPORT int lta_decode_attn_kv8s_pos(int dtype, const void* q, const void* k, const void* v, const void* k_scale,
                                         const void* v_scale, const void* pos, void* o, void* ws_acc, void* ws_ml, int B,
                                         int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides, int nsplit,
                                         float scale, int wsplit, void* stream) {
-  using namespace lta;
-  if (!e4m3_cache_ok(k, v, strides) || k_scale == nullptr || v_scale == nullptr) return (int)hipErrorInvalidValue;
-  const KVScales sc{(const uint8_t*)k_scale, (const uint8_t*)v_scale, strides[11], strides[12], strides[13],
-                    strides[14], strides[15], strides[16]};
-  return launch_pos<uint8_t, true>(dtype, q, k, v, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S, D, strides, nsplit, scale,
-                                   wsplit, (hipStream_t)stream, sc);
+  return lta::decode_entry<uint8_t, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq,
+                                                S, D, strides, 0, nsplit, 0, scale, wsplit, stream);
 }

@@ -356,24 +356,35 @@ int grid_for(int64_t total) {
     }                                                            \
   } while (0)
 
+// the k / v destination of the cache-writing entries out of strides[0..5] (k b,g,s | v b,g,s, in elements): 16-byte
+// stores need every one a multiple of 8
+static bool kv_dst(const int64_t* strides, KVDst& st) {
+  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return false;
+  st = KVDst{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  return true;
+}
+
+// ROWS: per-row positions, `rc` the caches' capacity (see RowsCap); cos / sin and pos are then indexed by b * Tn + t.
+template <bool ROWS>
 static int qkv_rope_fwd_launch(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_, void* q,
                                void* k, void* v, const int64_t* pos, KVDst st, int B, int Tn, int nh, int ng, int hs,
-                               int rope_n, hipStream_t stream) {
+                               int rope_n, hipStream_t stream, std::conditional_t<ROWS, RowsCap, NoRows> rc) {
   if (hs % 8 || rope_n % 16 || rope_n > hs) return -2;
+  if constexpr (ROWS)
+    if (pos == nullptr || rc.S < 0) return -2;
   const int sh = row_pair_shift(dtype, hs, rope_n);
   if (sh >= 0) {
     LTA_DISPATCH_TC(dtype, cdtype,
-                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false>), dim3(B * Tn), dim3(256), 0, stream,
-                                       (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
-                                       (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, Tn, nh, ng, hs, sh,
-                                       NoScale{}, NoRows{}));
+                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, T, false, ROWS>), dim3(B * Tn), dim3(256), 0,
+                                       stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
+                                       (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, Tn, nh, ng, hs, sh, NoScale{}, rc));
     return (int)hipGetLastError();
   }
   const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));
   LTA_DISPATCH_TC(dtype, cdtype,
-                  hipLaunchKernelGGL((qkv_rope_fwd_kernel<T, C>), dim3(grid_for(total)), dim3(256), 0, stream,
+                  hipLaunchKernelGGL((qkv_rope_fwd_kernel<T, C, ROWS>), dim3(grid_for(total)), dim3(256), 0, stream,
                                      (const T*)qkv, (const C*)cos_, (const C*)sin_, (T*)q, (T*)k, (T*)v, pos, st, B, Tn,
-                                     nh, ng, hs, rope_n, NoRows{}));
+                                     nh, ng, hs, rope_n, rc));
   return (int)hipGetLastError();
 }
 
@@ -381,8 +392,8 @@ LTA_EXPORT int lta_qkv_rope_fwd(int dtype, int cdtype, const void* qkv, const vo
                                 void* k, void* v, int B, int Tn, int nh, int ng, int hs, int rope_n,
                                 hipStream_t stream) {
   const int64_t sg = (int64_t)Tn * hs, sb = ng * sg;
-  return qkv_rope_fwd_launch(dtype, cdtype, qkv, cos_, sin_, q, k, v, nullptr, KVDst{sb, sg, hs, sb, sg, hs}, B, Tn,
-                             nh, ng, hs, rope_n, stream);
+  return qkv_rope_fwd_launch<false>(dtype, cdtype, qkv, cos_, sin_, q, k, v, nullptr, KVDst{sb, sg, hs, sb, sg, hs}, B,
+                                    Tn, nh, ng, hs, rope_n, stream, NoRows{});
 }
 
 // k/v written in place into caches kc/vc [B, ng, S, hs] (strides in elements, head dim contiguous and
@@ -390,53 +401,57 @@ LTA_EXPORT int lta_qkv_rope_fwd(int dtype, int cdtype, const void* qkv, const vo
 LTA_EXPORT int lta_qkv_rope_cache_fwd(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
                                       void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
                                       int Tn, int nh, int ng, int hs, int rope_n, hipStream_t stream) {
-  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
-  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
-  return qkv_rope_fwd_launch(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, (const int64_t*)pos, st, B, Tn, nh, ng, hs,
-                             rope_n, stream);
+  KVDst st;
+  if (!kv_dst(strides, st)) return -2;
+  return qkv_rope_fwd_launch<false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, (const int64_t*)pos, st, B, Tn, nh, ng,
+                                    hs, rope_n, stream, NoRows{});
 }
 
 // As lta_qkv_rope_cache_fwd with uint8 caches holding unscaled OCP e4m3: k (rotated) and v are rounded
 // to the activation dtype, saturated to +-448 and converted (round to nearest even), 8 bytes per store.
 // Row-kernel shapes only (rope_n == hs, hs / 16 a power of two, 16-bit activations): -2 otherwise.
-// KS: the scaled cache, its scale bytes through `sd`.
-template <bool KS>
+// KS: the scaled cache of ops/kv8.py: every k / v head row is stored as the bytes of x * 2^-e plus one scale
+// byte e + 127 in ksc / vsc [B, ng, S, 1] (uint8), whose strides follow the caches': k b,g,s | v b,g,s |
+// k scale b,g,s | v scale b,g,s.  A head row must fit one wave's lanes (hs <= 1024).
+// ROWS: as for qkv_rope_fwd_launch.
+template <bool KS, bool ROWS>
 static int qkv_rope_e4m3_launch(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_, void* q,
-                                void* kc, void* vc, const void* pos, const int64_t* strides, int B, int Tn, int nh,
-                                int ng, int hs, int rope_n, hipStream_t stream,
-                                std::conditional_t<KS, ScaleDst, NoScale> sd) {
-  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
-  if (((uintptr_t)kc | (uintptr_t)vc) % 8) return -2;
+                                void* kc, void* vc, void* ksc, void* vsc, const void* pos, const int64_t* strides,
+                                int B, int Tn, int nh, int ng, int hs, int rope_n, hipStream_t stream,
+                                std::conditional_t<ROWS, RowsCap, NoRows> rc) {
+  KVDst st;
+  if (!kv_dst(strides, st) || ((uintptr_t)kc | (uintptr_t)vc) % 8) return -2;
   const int sh = row_pair_shift(dtype, hs, rope_n);
   if (sh < 0 || dtype == kF32) return -2;
-  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
+  if constexpr (ROWS)
+    if (pos == nullptr || rc.S < 0) return -2;
+  std::conditional_t<KS, ScaleDst, NoScale> sd{};
+  if constexpr (KS) {
+    if (sh > 6 || (ROWS && (ksc == nullptr || vsc == nullptr))) return -2;
+    sd = ScaleDst{(uint8_t*)ksc, (uint8_t*)vsc, strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
+  }
   LTA_DISPATCH_TC(dtype, cdtype,
                   if constexpr (sizeof(T) == 2)  // fp32 activations were refused above: no such kernel is built
-                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, KS>), dim3(B * Tn), dim3(256), 0,
+                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, KS, ROWS>), dim3(B * Tn), dim3(256), 0,
                                        stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
                                        (const C*)sin_, (T*)q, (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn,
-                                       nh, ng, hs, sh, sd, NoRows{}));
+                                       nh, ng, hs, sh, sd, rc));
   return (int)hipGetLastError();
 }
 
 LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
                                           void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
                                           int Tn, int nh, int ng, int hs, int rope_n, hipStream_t stream) {
-  return qkv_rope_e4m3_launch<false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs, rope_n,
-                                     stream, NoScale{});
+  return qkv_rope_e4m3_launch<false, false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, nullptr, nullptr, pos, strides, B,
+                                            Tn, nh, ng, hs, rope_n, stream, NoRows{});
 }
 
-// As lta_qkv_rope_cache_fwd_kv8 for the scaled e4m3 cache of ops/kv8.py: every k / v head row is stored as
-// the bytes of x * 2^-e plus one scale byte e + 127 in ksc / vsc [B, ng, S, 1] (uint8).  `strides`: k b,g,s |
-// v b,g,s | k scale b,g,s | v scale b,g,s.  A head row must fit one wave's lanes (hs <= 1024).
 LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
                                            void* q, void* kc, void* vc, void* ksc, void* vsc, const void* pos,
                                            const int64_t* strides, int B, int Tn, int nh, int ng, int hs, int rope_n,
                                            hipStream_t stream) {
-  if (row_pair_shift(dtype, hs, rope_n) > 6) return -2;
-  const ScaleDst sd{(uint8_t*)ksc, (uint8_t*)vsc, strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
-  return qkv_rope_e4m3_launch<true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs, rope_n,
-                                    stream, sd);
+  return qkv_rope_e4m3_launch<true, false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, ksc, vsc, pos, strides, B, Tn, nh,
+                                           ng, hs, rope_n, stream, NoRows{});
 }
 
 // The per-row entries (a ragged batch): cos / sin [B*Tn, rope_n], pos int64 [B*Tn], both indexed by b * Tn + t,
@@ -445,62 +460,26 @@ LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s(int dtype, int cdtype, const void* qk
 LTA_EXPORT int lta_qkv_rope_cache_fwd_rows(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
                                            void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
                                            int Tn, int nh, int ng, int hs, int rope_n, int S, hipStream_t stream) {
-  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
-  if (hs % 8 || rope_n % 16 || rope_n > hs || pos == nullptr || S < 0) return -2;
-  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
-  const RowsCap rc{S};
-  const int sh = row_pair_shift(dtype, hs, rope_n);
-  if (sh >= 0) {
-    LTA_DISPATCH_TC(dtype, cdtype,
-                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, T, false, true>), dim3(B * Tn), dim3(256), 0,
-                                       stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
-                                       (const C*)sin_, (T*)q, (T*)kc, (T*)vc, (const int64_t*)pos, st, Tn, nh, ng, hs,
-                                       sh, NoScale{}, rc));
-    return (int)hipGetLastError();
-  }
-  const int64_t total = (int64_t)B * Tn * (nh + 2 * ng) * (hs / (dtype == kF32 ? 4 : 8));
-  LTA_DISPATCH_TC(dtype, cdtype,
-                  hipLaunchKernelGGL((qkv_rope_fwd_kernel<T, C, true>), dim3(grid_for(total)), dim3(256), 0, stream,
-                                     (const T*)qkv, (const C*)cos_, (const C*)sin_, (T*)q, (T*)kc, (T*)vc,
-                                     (const int64_t*)pos, st, B, Tn, nh, ng, hs, rope_n, rc));
-  return (int)hipGetLastError();
-}
-
-template <bool KS>
-static int qkv_rope_e4m3_rows_launch(int dtype, int cdtype, const void* qkv, const void* cos_, const void* sin_,
-                                     void* q, void* kc, void* vc, const void* pos, const int64_t* strides, int B,
-                                     int Tn, int nh, int ng, int hs, int rope_n, int S, hipStream_t stream,
-                                     std::conditional_t<KS, ScaleDst, NoScale> sd) {
-  if ((strides[0] | strides[1] | strides[2] | strides[3] | strides[4] | strides[5]) % 8) return -2;
-  if (((uintptr_t)kc | (uintptr_t)vc) % 8 || pos == nullptr || S < 0) return -2;
-  const int sh = row_pair_shift(dtype, hs, rope_n);
-  if (sh < 0 || dtype == kF32) return -2;
-  const KVDst st{strides[0], strides[1], strides[2], strides[3], strides[4], strides[5]};
-  LTA_DISPATCH_TC(dtype, cdtype,
-                  if constexpr (sizeof(T) == 2)
-                    hipLaunchKernelGGL((qkv_rope_row_kernel<T, C, false, uint8_t, KS, true>), dim3(B * Tn), dim3(256),
-                                       0, stream, (const T*)qkv, (const T*)nullptr, (const T*)nullptr, (const C*)cos_,
-                                       (const C*)sin_, (T*)q, (uint8_t*)kc, (uint8_t*)vc, (const int64_t*)pos, st, Tn,
-                                       nh, ng, hs, sh, sd, RowsCap{S}));
-  return (int)hipGetLastError();
+  KVDst st;
+  if (!kv_dst(strides, st)) return -2;
+  return qkv_rope_fwd_launch<true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, (const int64_t*)pos, st, B, Tn, nh, ng,
+                                   hs, rope_n, stream, RowsCap{S});
 }
 
 LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8_rows(int dtype, int cdtype, const void* qkv, const void* cos_,
                                                const void* sin_, void* q, void* kc, void* vc, const void* pos,
                                                const int64_t* strides, int B, int Tn, int nh, int ng, int hs,
                                                int rope_n, int S, hipStream_t stream) {
-  return qkv_rope_e4m3_rows_launch<false>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs,
-                                          rope_n, S, stream, NoScale{});
+  return qkv_rope_e4m3_launch<false, true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, nullptr, nullptr, pos, strides, B,
+                                           Tn, nh, ng, hs, rope_n, stream, RowsCap{S});
 }
 
 LTA_EXPORT int lta_qkv_rope_cache_fwd_kv8s_rows(int dtype, int cdtype, const void* qkv, const void* cos_,
                                                 const void* sin_, void* q, void* kc, void* vc, void* ksc, void* vsc,
                                                 const void* pos, const int64_t* strides, int B, int Tn, int nh, int ng,
                                                 int hs, int rope_n, int S, hipStream_t stream) {
-  if (row_pair_shift(dtype, hs, rope_n) > 6 || ksc == nullptr || vsc == nullptr) return -2;
-  const ScaleDst sd{(uint8_t*)ksc, (uint8_t*)vsc, strides[6], strides[7], strides[8], strides[9], strides[10], strides[11]};
-  return qkv_rope_e4m3_rows_launch<true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, pos, strides, B, Tn, nh, ng, hs,
-                                         rope_n, S, stream, sd);
+  return qkv_rope_e4m3_launch<true, true>(dtype, cdtype, qkv, cos_, sin_, q, kc, vc, ksc, vsc, pos, strides, B, Tn, nh,
+                                          ng, hs, rope_n, stream, RowsCap{S});
 }
 
 LTA_EXPORT int lta_qkv_rope_bwd(int dtype, int cdtype, const void* dq, const void* dk, const void* dv, const void* cos_,

@@ -10,10 +10,12 @@ from .kv8 import scale_caches_of
 
 register_signature("lta_qkv_rope_fwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
-# the cache-writing entries: pointers qkv, cos, sin, q, kc, vc, <scale caches>, pos, strides
+# the cache-writing entries: pointers qkv, cos, sin, q, kc, vc, <scale caches>, pos, strides; the per-row entries
+# take the caches' capacity S after rope_n
 for _entry, _scale_ptrs in (("lta_qkv_rope_cache_fwd", 0), ("lta_qkv_rope_cache_fwd_kv8", 0),
                             ("lta_qkv_rope_cache_fwd_kv8s", 2)):
     register_signature(_entry, [c_int, c_int, *[c_void_p] * (8 + _scale_ptrs), *[c_int] * 6, c_void_p])
+    register_signature(_entry + "_rows", [c_int, c_int, *[c_void_p] * (8 + _scale_ptrs), *[c_int] * 7, c_void_p])
 register_signature("lta_qkv_rope_bwd", [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int, c_int, c_int, c_int, c_int, c_int, c_void_p])
 register_signature("lta_swiglu_fwd", [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p])
@@ -86,6 +88,26 @@ def qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_
             and scale_caches_of((k_scale, v_scale), (kc, vc)))
 
 
+def _qkv_rope_cache_launch(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, caches, pos, suffix="", *capacity):
+    """One launch of the cache-writing entry for ``caches`` = (kc, vc) or (kc, vc, k_scale, v_scale), over contiguous
+    qkv / cos / sin / pos; the per-row entries have the ``suffix`` "_rows" and take the caches' ``capacity`` after
+    rope_n.  Returns (q, *caches)."""
+    lib = require()
+    B, T, _ = qkv.shape
+    if cos.dtype != sin.dtype:
+        sin = sin.to(cos.dtype)
+    if cos.dtype not in (torch.float32, qkv.dtype):
+        cos, sin = cos.float(), sin.float()
+    q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
+    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches for s in c.stride()[:3]))
+    entry = ("lta_qkv_rope_cache_fwd" + ("_kv8s" if len(caches) == 4 else "_kv8" if caches[0].dtype == torch.uint8 else "")
+             + suffix)
+    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), *map(ptr, caches), ptr(pos),
+                             st, B, T, n_head, n_query_groups, head_size, rope_n, *capacity, stream_ptr(qkv.device))
+    check(rc, entry)
+    return (q, *caches)
+
+
 def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kc, vc, pos,
                        k_scale=None, v_scale=None):
     """qkv split + RoPE with k / v written in place into the static caches ``kc`` / ``vc`` at rows
@@ -102,29 +124,9 @@ def qkv_rope_cache_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_siz
                                                       rope_n):
         raise ValueError("qkv_rope_cache_fwd: operands the scaled e4m3 write does not take "
                          "(see qkv_rope_cache_scaled_supported)")
-    lib = require()
-    qkv = _c(qkv)
-    B, T, _ = qkv.shape
-    cos = _c(cos[:T])
-    sin = _c(sin[:T])
-    if cos.dtype != sin.dtype:
-        sin = sin.to(cos.dtype)
-    if cos.dtype not in (torch.float32, qkv.dtype):
-        cos, sin = cos.float(), sin.float()
-    q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
-    caches = (kc, vc, *scales)
-    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches for s in c.stride()[:3]))
-    entry = "lta_qkv_rope_cache_fwd" + ("_kv8s" if scales else "_kv8" if kc.dtype == torch.uint8 else "")
-    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), *map(ptr, caches), ptr(pos),
-                             st, B, T, n_head, n_query_groups, head_size, rope_n, stream_ptr(qkv.device))
-    check(rc, entry)
-    return (q, *caches)
-
-
-# the per-row entries: the same pointers, and the caches' capacity S after rope_n
-for _entry, _scale_ptrs in (("lta_qkv_rope_cache_fwd_rows", 0), ("lta_qkv_rope_cache_fwd_kv8_rows", 0),
-                            ("lta_qkv_rope_cache_fwd_kv8s_rows", 2)):
-    register_signature(_entry, [c_int, c_int, *[c_void_p] * (8 + _scale_ptrs), *[c_int] * 7, c_void_p])
+    T = qkv.shape[1]
+    return _qkv_rope_cache_launch(_c(qkv), _c(cos[:T]), _c(sin[:T]), n_head, n_query_groups, head_size, rope_n,
+                                  (kc, vc, *scales), pos)
 
 
 def qkv_rope_cache_rows_supported(qkv, cos, sin, kc, vc, pos, n_query_groups: int, head_size: int,
@@ -161,22 +163,8 @@ def qkv_rope_cache_rows_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, hea
         raise ValueError("qkv_rope_cache_rows_fwd: operands the per-row write does not take "
                          "(see qkv_rope_cache_rows_supported)")
     scales = () if k_scale is None else (k_scale, v_scale)
-    lib = require()
-    qkv = _c(qkv)
-    B, T, _ = qkv.shape
-    cos, sin, pos = _c(cos), _c(sin), _c(pos)
-    if cos.dtype != sin.dtype:
-        sin = sin.to(cos.dtype)
-    if cos.dtype not in (torch.float32, qkv.dtype):
-        cos, sin = cos.float(), sin.float()
-    q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
-    caches = (kc, vc, *scales)
-    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches for s in c.stride()[:3]))
-    entry = "lta_qkv_rope_cache_fwd" + ("_kv8s" if scales else "_kv8" if kc.dtype == torch.uint8 else "") + "_rows"
-    rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), *map(ptr, caches), ptr(pos),
-                             st, B, T, n_head, n_query_groups, head_size, rope_n, kc.shape[2], stream_ptr(qkv.device))
-    check(rc, entry)
-    return (q, *caches)
+    return _qkv_rope_cache_launch(_c(qkv), _c(cos), _c(sin), n_head, n_query_groups, head_size, rope_n,
+                                  (kc, vc, *scales), _c(pos), "_rows", kc.shape[2])
 
 
 def qkv_rope_rows_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int):

@@ -43,7 +43,7 @@ def _position_sets(B, T, S):
     want = want[:max(6, min(n, len(want)))]
     sets = []
     for i in range(0, len(want), n):
-        vals = (want[i:i + n] + want)[:n]  # the last set is topped up from the front
+        vals = (want[i:i + n] + want * (n // len(want) + 1))[:n]  # topped up from the front, round and round
         sets.append(torch.tensor(vals, dtype=torch.int64).view(B, T))
     assert {int(v) for s in sets for v in s.flatten()} >= {0, 63, 64, 5, S - 7, S - 1}
     return sets
@@ -208,6 +208,47 @@ def test_e4m3_position_kernels_equal_the_16_bit_one_bit_for_bit(shape, fmt, D, d
     assert {c[0] for c in pos_spy} == {ENTRY[fmt], ENTRY["16bit"]}
 
 
+# operator (executors/hipex.py ``_decode_attn_<op>_impl``, ops/attention.py ``decode_attn_<op>_supported``) ->
+# (cache format, whether it takes positions in place of a mask)
+DECLINING = {"kv8": ("kv8", False), "kv8s": ("kv8s", False), "pos": ("16bit", True), "kv8_pos": ("kv8", True),
+             "kv8s_pos": ("kv8s", True)}
+
+
+@gpu
+@pytest.mark.parametrize("op", list(DECLINING))
+def test_decode_operators_decline_17_query_rows(op, pos_spy):
+    """One query row more than the e4m3 and position kernels take: ``*_supported`` refuses, the operator launches
+    none of those entries and runs the program as the model spells it, the 16-bit mask kernel (which takes any row
+    count) over the dequantised cache under the caller's mask, or under ``position_mask`` for the position forms."""
+    from lightning_thunder_amd.executors import hipex
+    from lightning_thunder_amd.ops import attention as A
+    from lightning_thunder_amd.ops.kv_rows import position_mask
+
+    fmt, by_pos = DECLINING[op]
+    B, Hq, Hkv, T, S, D, dtype = 1, 4, 2, A.DECODE_MAX_QUERIES + 1, 96, 64, BF16
+    assert T == 17
+    q, caches, exact = _kv_case(B, Hq, Hkv, T, S, D, dtype, fmt, seed=4)
+    q = q.cuda()
+    caches = [c.cuda() for c in caches]
+    kd, vd = (e.to(dtype).cuda() for e in exact)
+    assert torch.equal(kd.float().cpu(), exact[0]) and torch.equal(vd.float().cpu(), exact[1])
+    impl, supported = getattr(hipex, f"_decode_attn_{op}_impl"), getattr(A, f"decode_attn_{op}_supported")
+    # the fixture bars the three mask entries; the fallback is the 16-bit one, the format's own stays barred
+    pos_spy.monkeypatch.setattr(pos_spy.lib, "lta_decode_attn", pos_spy.mask_entries["lta_decode_attn"])
+    for n, pos in enumerate(_position_sets(B, T, S)):
+        pos = pos.cuda()
+        mask = position_mask(pos, S)
+        if by_pos:
+            assert not supported(q, *caches, pos)
+            out = impl(q, *caches, pos, None)
+        else:
+            assert not supported(q, *caches)
+            out = impl(q, *caches, mask, False, None)
+        assert list(pos_spy) == [], f"a position entry ran: {list(pos_spy)}"
+        ref = A.decode_attn(q, kd, vd, mask)
+        assert out.shape == q.shape and bits_equal(out, ref), f"set {n}: {(out != ref).sum().item()} elements differ"
+
+
 @gpu
 @pytest.mark.parametrize("fmt", FORMATS)
 @pytest.mark.parametrize("shape", ["wsplit_split_t3", "rows4"])
@@ -281,10 +322,8 @@ def _rope_caches(fmt, B, ng, S, hs, dtype):
     return views, bufs
 
 
-def _check_rope_rows(fmt, B, T, nh, ng, hs, dtype, cos_dtype, pos, monkeypatch):
-    from lightning_thunder_amd.ops import require
-    from lightning_thunder_amd.ops.fused import qkv_rope_cache_rows_fwd, qkv_rope_cache_rows_supported, qkv_rope_fwd
-
+def _rope_rows_inputs(B, T, nh, ng, hs, dtype, cos_dtype, pos):
+    """(qkv [B, T, (nh + 2 ng) hs], cos and sin [B, T, hs] gathered per token, pos int64 [B, T]) on the GPU."""
     S = ROPE_S
     g = torch.Generator().manual_seed(hs + T)
     qkv = (torch.randn(B, T, (nh + 2 * ng) * hs, generator=g) * 4).to(dtype).cuda()
@@ -292,21 +331,15 @@ def _check_rope_rows(fmt, B, T, nh, ng, hs, dtype, cos_dtype, pos, monkeypatch):
     sin_tab = (torch.rand(S, hs, generator=g) * 2 - 1).to(cos_dtype).cuda()
     pos = torch.tensor(pos, dtype=torch.int64, device="cuda")
     rot = pos.clamp(0, S - 1)  # a token outside the cache still gets a rotation for its q row
-    cos, sin = cos_tab[rot], sin_tab[rot]  # [B, T, hs]
-    caches, bufs = _rope_caches(fmt, B, ng, S, hs, dtype)
-    scales = dict(k_scale=caches[2], v_scale=caches[3]) if fmt == "kv8s" else {}
-    assert qkv_rope_cache_rows_supported(qkv, cos, sin, caches[0], caches[1], pos, ng, hs, hs, **scales)
-    lib = require()
-    calls = []
-    for name in ROPE_ENTRY.values():
-        monkeypatch.setattr(lib, name, lambda *a, _r=getattr(lib, name), _n=name: calls.append(_n) or _r(*a))
-    for name in ("lta_qkv_rope_cache_fwd", "lta_qkv_rope_cache_fwd_kv8", "lta_qkv_rope_cache_fwd_kv8s"):
-        monkeypatch.setattr(lib, name, lambda *a, _n=name: pytest.fail(f"per-row positions reached {_n}"))
-    q, *got = qkv_rope_cache_rows_fwd(qkv, cos, sin, nh, ng, hs, hs, caches[0], caches[1], pos, **scales)
-    assert calls == [ROPE_ENTRY[fmt]]
-    for g_, src in zip(got, caches):
-        assert g_.data_ptr() == src.data_ptr() and g_.stride() == src.stride()
-    # per sequence: the shared-position kernel's rows, stored as the format stores them
+    return qkv, cos_tab[rot], sin_tab[rot], pos
+
+
+def _assert_rope_rows(fmt, qkv, cos, sin, pos, nh, ng, hs, q, bufs):
+    """``q`` and the cache buffers ``bufs`` against the shared-position kernel per sequence, its rows stored as the
+    format stores them at the positions inside the cache, the sentinel everywhere else.  Returns the rows written."""
+    from lightning_thunder_amd.ops.fused import qkv_rope_fwd
+
+    (B, T), S, dtype = pos.shape, ROPE_S, qkv.dtype
     exp_caches, exp_bufs = _rope_caches(fmt, B, ng, S, hs, dtype)
     written = 0
     for b in range(B):
@@ -323,6 +356,29 @@ def _check_rope_rows(fmt, B, T, nh, ng, hs, dtype, cos_dtype, pos, monkeypatch):
     assert written == int(((pos >= 0) & (pos < S)).sum())
     for name, got_b, exp_b in zip(("k", "v", "k_scale", "v_scale"), bufs, exp_bufs):
         assert torch.equal(got_b, exp_b), f"the {name} cache differs from the per-sequence rows (or a store strayed)"
+    return written
+
+
+def _check_rope_rows(fmt, B, T, nh, ng, hs, dtype, cos_dtype, pos, monkeypatch):
+    from lightning_thunder_amd.ops import require
+    from lightning_thunder_amd.ops.fused import qkv_rope_cache_rows_fwd, qkv_rope_cache_rows_supported
+
+    S = ROPE_S
+    qkv, cos, sin, pos = _rope_rows_inputs(B, T, nh, ng, hs, dtype, cos_dtype, pos)
+    caches, bufs = _rope_caches(fmt, B, ng, S, hs, dtype)
+    scales = dict(k_scale=caches[2], v_scale=caches[3]) if fmt == "kv8s" else {}
+    assert qkv_rope_cache_rows_supported(qkv, cos, sin, caches[0], caches[1], pos, ng, hs, hs, **scales)
+    lib = require()
+    calls = []
+    for name in ROPE_ENTRY.values():
+        monkeypatch.setattr(lib, name, lambda *a, _r=getattr(lib, name), _n=name: calls.append(_n) or _r(*a))
+    for name in ("lta_qkv_rope_cache_fwd", "lta_qkv_rope_cache_fwd_kv8", "lta_qkv_rope_cache_fwd_kv8s"):
+        monkeypatch.setattr(lib, name, lambda *a, _n=name: pytest.fail(f"per-row positions reached {_n}"))
+    q, *got = qkv_rope_cache_rows_fwd(qkv, cos, sin, nh, ng, hs, hs, caches[0], caches[1], pos, **scales)
+    assert calls == [ROPE_ENTRY[fmt]]
+    for g_, src in zip(got, caches):
+        assert g_.data_ptr() == src.data_ptr() and g_.stride() == src.stride()
+    written = _assert_rope_rows(fmt, qkv, cos, sin, pos, nh, ng, hs, q, bufs)
     if fmt == "16bit":
         for buf in bufs:
             assert_guard_intact(buf, (B, ng, S, hs), "rope rows")
@@ -338,6 +394,34 @@ def _check_rope_rows(fmt, B, T, nh, ng, hs, dtype, cos_dtype, pos, monkeypatch):
 def test_qkv_rope_cache_rows(fmt, hs, T, same_cos, dtype, monkeypatch):
     n = _check_rope_rows(fmt, 3, T, 4, 2, hs, dtype, dtype if same_cos else F32, ROPE_POS[T], monkeypatch)
     assert n == 3 * T
+
+
+@gpu
+@pytest.mark.parametrize("fmt", ["kv8", "kv8s"])
+def test_qkv_rope_cache_rows_operators_decline_hs96(fmt, monkeypatch):
+    """hs = 96 is no row-kernel shape, so ``qkv_rope_cache_rows_supported`` refuses uint8 caches and the per-row
+    operators write what the model's program writes (RoPE, quantise, one row write per buffer) without an e4m3
+    rows launch.  One uint8 cache beside a 16-bit one is refused."""
+    from lightning_thunder_amd.executors.hipex import _qkv_rope_cache_rows_impl, _qkv_rope_cache_rows_s8_impl
+    from lightning_thunder_amd.ops import require
+    from lightning_thunder_amd.ops.fused import qkv_rope_cache_rows_supported
+
+    B, T, nh, ng, hs, dtype = 3, 2, 4, 2, 96, BF16
+    qkv, cos, sin, pos = _rope_rows_inputs(B, T, nh, ng, hs, dtype, F32, ROPE_POS[T])
+    caches, bufs = _rope_caches(fmt, B, ng, ROPE_S, hs, dtype)
+    scales = dict(k_scale=caches[2], v_scale=caches[3]) if fmt == "kv8s" else {}
+    assert not qkv_rope_cache_rows_supported(qkv, cos, sin, caches[0], caches[1], pos, ng, hs, hs, **scales)
+    lib = require()
+    for name in (ROPE_ENTRY["kv8"], ROPE_ENTRY["kv8s"]):
+        monkeypatch.setattr(lib, name, lambda *a, _n=name: pytest.fail(f"an unsupported shape reached {_n}"))
+    impl = _qkv_rope_cache_rows_s8_impl if fmt == "kv8s" else _qkv_rope_cache_rows_impl
+    q, *got = impl(qkv, cos, sin, nh, ng, hs, hs, *caches, pos)
+    assert [t.data_ptr() for t in got] == [t.data_ptr() for t in caches]
+    assert _assert_rope_rows(fmt, qkv, cos, sin, pos, nh, ng, hs, q, bufs) == B * T
+    if fmt == "kv8":
+        with pytest.raises(ValueError):
+            _qkv_rope_cache_rows_impl(qkv, cos, sin, nh, ng, hs, hs, caches[0], torch.zeros_like(caches[1], dtype=dtype),
+                                      pos)
 
 
 @gpu
