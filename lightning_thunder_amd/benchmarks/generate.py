@@ -36,7 +36,8 @@ import torch
 from . import KV_CACHE_FORMATS
 
 
-def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model", batch_size: int = 1):
+def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model", batch_size: int = 1,
+           page_size=None, num_pages=None):
     from ..models.litgpt import GPT, Config, init_weights
 
     kw = {} if n_layer is None else {"n_layer": n_layer}
@@ -48,7 +49,8 @@ def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: 
     init_weights(model)
     model.requires_grad_(False)
     model.eval()
-    model.set_kv_cache(batch_size, max_seq, device=device, **KV_CACHE_FORMATS[kv_cache_dtype])
+    model.set_kv_cache(batch_size, max_seq, device=device, page_size=page_size, num_pages=num_pages,
+                       **KV_CACHE_FORMATS[kv_cache_dtype])
     return model, cfg
 
 
@@ -93,7 +95,7 @@ def run(mode: str, args) -> dict:
             return gm.generate(prompt, **kw)
     else:
         model, cfg = _build(args.model, args.prompt_len + args.new_tokens + 8, device, args.n_layer, args.kv_cache_dtype,
-                            args.batch_size)
+                            args.batch_size, args.kv_page_size, args.kv_num_pages)
         prompt = torch.randint(0, cfg.vocab_size, (args.batch_size, args.prompt_len), device=device)
         lengths = None
         if args.prompt_lengths is not None:
@@ -146,6 +148,12 @@ def run(mode: str, args) -> dict:
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
         "reference_ms": {"thunder+cudagraphs (1xH100)": 542, "eager (1xH100)": 1493},
     }
+    if not mode.startswith("hf_"):
+        caches = [b.attn.kv_cache for b in model.transformer.h]
+        res["kv_cache_gib"] = round(sum(t.numel() * t.element_size() for c in caches for t in c.buffers()) / 2 ** 30, 3)
+        pages = model.kv_pages
+        res.update(kv_page_size=args.kv_page_size, kv_num_pages=None if pages is None else pages.num_pages,
+                   kv_pages_in_use=None if pages is None else pages.pages_in_use)
     if sampling:
         res.update(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     first_new = args.prompt_lengths[0] if args.prompt_lengths and not mode.startswith("hf_") else out.shape[1] - args.new_tokens
@@ -182,7 +190,16 @@ def main(argv=None):
     p.add_argument("--prompt-lengths", default=None,
                    help="LitGPT modes: a,b,c,... one prompt length per sequence (a ragged batch, right-padded to the "
                         "longest, which replaces --prompt-len); --batch-size must match")
+    p.add_argument("--kv-page-size", type=int, default=None,
+                   help="LitGPT modes: a power of two >= 16: a paged KV cache (pools of pages and a block table) "
+                        "instead of the static one")
+    p.add_argument("--kv-num-pages", type=int, default=None,
+                   help="pages per pool of a paged cache (default: what the static cache would hold)")
     args = p.parse_args(argv)
+    if args.kv_num_pages is not None and args.kv_page_size is None:
+        p.error("--kv-num-pages needs --kv-page-size")
+    if args.kv_page_size is not None and any(m.startswith("hf_") for m in args.modes.split(",")):
+        p.error("--kv-page-size is for the LitGPT modes")
     if args.prompt_lengths is not None:
         try:
             args.prompt_lengths = [int(x) for x in args.prompt_lengths.split(",")]

@@ -49,7 +49,7 @@ def _build(args, device):
     model.requires_grad_(False)
     model.eval()
     model.set_kv_cache(args.batch_size, args.input_length + args.output_length + 8, device=device,
-                       **KV_CACHE_FORMATS[args.kv_cache_dtype])
+                       page_size=args.kv_page_size, num_pages=args.kv_num_pages, **KV_CACHE_FORMATS[args.kv_cache_dtype])
     return model, cfg
 
 
@@ -78,9 +78,13 @@ def run(mode: str, args) -> dict:
     gen = torch.Generator(device).manual_seed(1)
     prompt = torch.randint(0, cfg.vocab_size, (args.batch_size, args.input_length), device=device, generator=gen)
     prefill_pos = torch.arange(args.input_length, device=device)
-    ragged = args.prompt_lengths is not None
+    pages = model.kv_pages  # a paged cache (--kv-page-size) takes one position per token: the ragged route
+    ragged = args.prompt_lengths is not None or pages is not None
+    host_lengths = args.prompt_lengths or [args.input_length] * args.batch_size
+    if pages is not None:
+        prefill_pos = prefill_pos.expand(args.batch_size, -1).contiguous()
     if ragged:
-        lengths = torch.tensor(args.prompt_lengths, dtype=torch.int64, device=device)
+        lengths = torch.tensor(host_lengths, dtype=torch.int64, device=device)
         last = lengths - 1
         rows = torch.arange(args.batch_size, device=device)
         pos = torch.empty((args.batch_size, 1), dtype=torch.int64, device=device)
@@ -88,8 +92,13 @@ def run(mode: str, args) -> dict:
         pos = torch.empty(1, dtype=torch.int64, device=device)
 
     def iteration():
+        if pages is not None:
+            pages.reset()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if pages is not None:
+            held = list(host_lengths)
+            pages.reserve(held)
         logits = fwd(prompt, prefill_pos)
         tok = argmax_last(logits[rows, last] if ragged else logits[:, -1], keepdim=True)
         torch.cuda.synchronize()
@@ -101,6 +110,9 @@ def run(mode: str, args) -> dict:
         steps = []
         for _ in range(args.output_length - 1):
             t1 = time.perf_counter()
+            if pages is not None:  # room for this step's token, from host-side counters
+                held = [n + 1 for n in held]
+                pages.reserve(held)
             logits = fwd(tok, pos)
             tok = argmax_last(logits[:, -1], keepdim=True)
             pos.add_(1)
@@ -138,6 +150,8 @@ def run(mode: str, args) -> dict:
         "dtype": "bf16", "kv_cache_dtype": args.kv_cache_dtype,
         "kv_cache_gib": round(sum(c.numel() * c.element_size() for b in model.transformer.h
                                   for c in b.attn.kv_cache.buffers()) / 2 ** 30, 3),  # scale buffers included
+        "kv_page_size": args.kv_page_size, "kv_num_pages": None if pages is None else pages.num_pages,
+        "kv_pages_in_use": None if pages is None else pages.pages_in_use,
         "memory_allocated_gib": round(torch.cuda.memory_allocated(device) / 2 ** 30, 3),  # held after the last step
         "max_memory_allocated_gib": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 3),
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
@@ -160,7 +174,14 @@ def main(argv=None):
     p.add_argument("--prompt-lengths", default=None,
                    help="a,b,c,...: one prompt length per sequence (a ragged batch, right-padded to the longest); "
                         "--batch-size must match")
+    p.add_argument("--kv-page-size", type=int, default=None,
+                   help="a power of two >= 16: a paged KV cache (pools of pages and a block table) instead of the "
+                        "static one")
+    p.add_argument("--kv-num-pages", type=int, default=None,
+                   help="pages per pool of a paged cache (default: what the static cache would hold)")
     args = p.parse_args(argv)
+    if args.kv_num_pages is not None and args.kv_page_size is None:
+        p.error("--kv-num-pages needs --kv-page-size")
     if args.output_length < 1:
         p.error("--output-length must be >= 1")
     if args.prompt_lengths is not None:

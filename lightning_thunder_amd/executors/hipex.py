@@ -15,7 +15,7 @@ from typing import Callable, NamedTuple
 import torch
 
 from ..core.prims import OpTags
-from ..core.proxies import TensorProxy, pyval
+from ..core.proxies import Proxy, TensorProxy, pyval
 from ..core import dtypes
 from ..extend import OperatorExecutor, register_executor, add_default_executor
 from ..ops.kv8 import E4M3_MAX
@@ -916,12 +916,17 @@ def _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_
 def _qkv_rope_cache_run(rope_args, caches, pos, stored, rows=False):
     """The cache-writing RoPE over ``caches`` in operator order (kc, vc, then scale caches): the kernel where its
     ``*_supported`` takes the operands, else the program as the model spells it (RoPE, then one write per buffer),
-    with ``stored(t)`` the tensors k (or v) goes into its caches as.  ``rows``: ``pos`` is per token, int64 [B, T]."""
+    with ``stored(t)`` the tensors k (or v) goes into its caches as.  ``rows``: ``pos`` is per token, int64 [B, T];
+    ``rows="slots"``: the caches are the pools of a paged cache and ``pos`` holds every token's pool row."""
     from ..ops import fused
+    from ..ops.kv_pages import write_slots
     from ..ops.kv_rows import write_rows
 
     qkv, cos, sin, _, *shape = rope_args
-    if rows:
+    if rows == "slots":
+        ok = fused.qkv_rope_cache_slots_supported(qkv, cos, sin, *caches[:2], pos, *shape, *caches[2:])
+        native, write = fused.qkv_rope_cache_slots_fwd, write_slots
+    elif rows:
         ok = fused.qkv_rope_cache_rows_supported(qkv, cos, sin, *caches[:2], pos, *shape, *caches[2:])
         native, write = fused.qkv_rope_cache_rows_fwd, write_rows
     else:
@@ -997,6 +1002,34 @@ hip_qkv_rope_cache_rows_s8 = ex.register_operator("hip_qkv_rope_cache_rows_s8", 
                                                   fn=_qkv_rope_cache_rows_s8_impl,
                                                   tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
 hip_qkv_rope_cache_rows_s8.written_args = (7, 8, 9, 10)
+# A paged cache (ops/kv_pages.py): the caches are pools [ng, R + 1, hs] and ``slots`` int64 [B, T] holds every token's
+# pool row; the same per-row entries of csrc/rope.hip, with the pools' (0, head, row) strides and the capacity R.
+def _qkv_rope_cache_slots_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kp, vp, slots):
+    return _qkv_rope_cache_meta(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kp, vp, slots)
+
+
+def _qkv_rope_cache_slots_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kp, vp, slots):
+    return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n), (kp, vp), slots,
+                               _unscaled_stored("hip_qkv_rope_cache_slots", kp, vp), rows="slots")
+
+
+def _qkv_rope_cache_slots_s8_impl(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, kp, vp, k_scale, v_scale,
+                                  slots):
+    from ..ops.kv8 import quantise_rows
+
+    return _qkv_rope_cache_run((qkv, cos, sin, n_head, n_query_groups, head_size, rope_n),
+                               (kp, vp, k_scale, v_scale), slots, quantise_rows, rows="slots")
+
+
+hip_qkv_rope_cache_slots = ex.register_operator("hip_qkv_rope_cache_slots", meta=_qkv_rope_cache_slots_meta,
+                                                fn=_qkv_rope_cache_slots_impl, tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
+hip_qkv_rope_cache_slots.written_args = (7, 8)
+hip_qkv_rope_cache_slots_s8 = ex.register_operator("hip_qkv_rope_cache_slots_s8", meta=_qkv_rope_cache_s8_meta,
+                                                   fn=_qkv_rope_cache_slots_s8_impl,
+                                                   tags=(OpTags.DONT_DCE, OpTags.IN_PLACE))
+hip_qkv_rope_cache_slots_s8.written_args = (7, 8, 9, 10)
+_KV_PAGED_GATHER_IDS = ("custom_op.lta::kv_paged_gather", "custom_op.custom_op_impl_custom_op_lta_kv_paged_gather")
+_KV_PAGED_MASK_IDS = ("custom_op.lta::kv_paged_mask", "custom_op.custom_op_impl_custom_op_lta_kv_paged_mask")
 _KV_POSITION_MASK_IDS = ("custom_op.lta::kv_position_mask", "custom_op.custom_op_impl_custom_op_lta_kv_position_mask")
 _CACHE_WRITES = ("index_copy_inplace", "scatter_rows_inplace")  # shared positions / one position per token
 _KV8_QUANTISE_IDS = ("custom_op.lta::kv8_quantise_rows", "custom_op.custom_op_impl_custom_op_lta_kv8_quantise_rows")
@@ -1014,6 +1047,57 @@ def _kv_pos_fusion_off() -> bool:
     """LTA_KV_POS_FUSION=0 keeps a ragged batch's position mask and per-row cache writes as the separate operations
     the model spells (A/B against the per-row RoPE write and the position mode of the decode kernels)."""
     return os.environ.get("LTA_KV_POS_FUSION", "1") == "0"
+
+
+def _kv_paged_fusion_off() -> bool:
+    """LTA_KV_PAGED_FUSION=0 keeps a paged cache's slot writes, page gathers and mask as the separate operations the
+    model spells (A/B against the slot-writing RoPE and the paged mode of the decode kernels)."""
+    return os.environ.get("LTA_KV_PAGED_FUSION", "1") == "0"
+
+
+def _ints_of(args):
+    """The ints of ``f(x, 1, 0, 2)`` or ``f(x, (1, 0, 2))`` after the tensor, None for anything else."""
+    rest = args[1:]
+    if len(rest) == 1 and isinstance(rest[0], (tuple, list)):
+        rest = rest[0]
+    return tuple(rest) if all(isinstance(n, int) and not isinstance(n, bool) for n in rest) else None
+
+
+def _slot_relayout(rw, t):
+    """``(permute position, reshape position, the [H, B * T, D] tensor)`` when ``t`` [B, H, T, D] is read once, by
+    ``permute(t, 1, 0, 2, 3)``, whose result is read once by ``reshape(., H, B * T, D)`` (the layout a paged
+    cache's pools are written in, ops/kv_pages.py ``write_slots``); None for anything else."""
+    if getattr(t, "ndim", 0) != 4:
+        return None
+    B, H, T, D = t.shape
+    found = []
+    for names, ints, shape in ((("permute", "torch_permute"), (1, 0, 2, 3), (H, B, T, D)),
+                               (("reshape", "torch_reshape"), (H, B * T, D), (H, B * T, D))):
+        if rw.uses(t) != 1:
+            return None
+        (j,) = rw.consumers(t)
+        b = rw.bsyms[j]
+        if rw.touched(j) or b.sym.name not in names or b.kwargs or not b.args or b.args[0] is not t:
+            return None
+        if _ints_of(b.args) != ints or not isinstance(b.output, TensorProxy) or tuple(b.output.shape) != shape:
+            return None
+        found.append(j)
+        t = b.output
+    return (*found, t)
+
+
+def _flat_slots(rw, index):
+    """``(slots, reshape position)`` when ``index = reshape(slots, -1)`` of int64 ``slots`` [B, T], else None."""
+    j = rw.producer(index)
+    if j is None or rw.touched(j):
+        return None
+    b = rw.bsyms[j]
+    if b.sym.name not in ("reshape", "torch_reshape") or b.kwargs or not b.args or _ints_of(b.args) != (-1,):
+        return None
+    slots = b.args[0]
+    if not isinstance(slots, TensorProxy) or slots.dtype != torch.int64 or slots.ndim != 2:
+        return None
+    return slots, j
 
 
 def _only_tensor_arg(b, rest=0):
@@ -1058,7 +1142,7 @@ def _cache_sources(rw, t):
     else, and for both e4m3 kinds under LTA_KV8_FUSION=0."""
     (j,) = rw.consumers(t)
     b = rw.bsyms[j]
-    if b.sym.name in _CACHE_WRITES:
+    if b.sym.name in _CACHE_WRITES or _slot_relayout(rw, t) is not None:  # written as it is (a paged cache: relaid)
         return "plain", (t,), ()
     if _kv8_fusion_off():
         return None
@@ -1090,8 +1174,15 @@ def _fuse_kv_cache_writes(trace):
 
     A ragged batch the same way: the RoPE takes cos / sin ``[B, T, rope_n]``, every copied tensor is read once by a
     ``scatter_rows_inplace`` at one int64 ``pos`` ``[B, T]``, and the result is ``hip_qkv_rope_cache_rows`` (or
-    ``hip_qkv_rope_cache_rows_s8``).  LTA_KV_POS_FUSION=0 leaves those writes alone."""
+    ``hip_qkv_rope_cache_rows_s8``).  LTA_KV_POS_FUSION=0 leaves those writes alone.
+
+    A paged cache (ops/kv_pages.py), again with cos / sin ``[B, T, rope_n]``: every copied tensor is read once by the
+    ``[H, B * T, D]`` relayout (``_slot_relayout``), and that once by ``index_copy_inplace(pool, 1, reshape(slots,
+    -1), .)`` into a 3-D pool of its dtype, all at one int64 ``slots`` ``[B, T]``: ``hip_qkv_rope_cache_slots`` (or
+    ``hip_qkv_rope_cache_slots_s8``).  The relayouts go; ``reshape(slots, -1)`` goes with its last reader.
+    LTA_KV_PAGED_FUSION=0 leaves those writes alone."""
     rw = Rewrite(trace, ex)
+    flats = set()  # positions of the reshape(slots, -1) whose writes were folded
     for i, b in enumerate(rw.bsyms):
         if b.sym is not hip_qkv_rope:
             continue
@@ -1104,21 +1195,35 @@ def _fuse_kv_cache_writes(trace):
         srcs = [t for pair in zip(sk[1], sv[1]) for t in pair]  # the operators' order: k, v, then their scales
         copies, pos = [], None
         rows = getattr(b.args[1], "ndim", 2) == 3  # cos [B, T, rope_n]: one position per token
-        if rows and _kv_pos_fusion_off():
+        relayouts = [_slot_relayout(rw, t) if rows else None for t in srcs]
+        paged = relayouts[0] is not None  # the writes of a paged cache: all of one kind, or nothing is folded
+        if any((r is not None) != paged for r in relayouts):
             continue
-        for t in srcs:
+        if rows and (_kv_paged_fusion_off() if paged else _kv_pos_fusion_off()):
+            continue
+        links, flat_at = [], set()
+        for t, relayout in zip(srcs, relayouts):
+            if paged:
+                *hops, t = relayout
+                links += hops
             if rw.uses(t) != 1:
                 break
             (j,) = rw.consumers(t)
             c = rw.bsyms[j]
-            if rw.touched(j) or c.sym.name != _CACHE_WRITES[rows]:
+            if rw.touched(j) or c.sym.name != _CACHE_WRITES[rows and not paged]:
                 break
             w = operands(c)
-            buf, index = w["buf"], w["pos" if rows else "index"]
-            if not rows and w["dim"] != 2:
+            buf, index = w["buf"], w["pos" if rows and not paged else "index"]
+            if not (rows and not paged) and w["dim"] != (1 if paged else 2):
                 break
             if w["src"] is not t or not isinstance(buf, TensorProxy) or buf.dtype != t.dtype:
                 break
+            if paged:  # a pool [ng, R + 1, hs], written at reshape(slots, -1)
+                flat = _flat_slots(rw, index) if isinstance(index, TensorProxy) else None
+                if flat is None or buf.ndim != 3:
+                    break
+                index = flat[0]
+                flat_at.add(flat[1])
             if pos is None:
                 pos = index
                 if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or (rows and pos.ndim != 2):
@@ -1142,10 +1247,14 @@ def _fuse_kv_cache_writes(trace):
             lo = min(at_copies)
             if any(lo < j < at and j not in at_copies for t in (*outs, *bufs) for j in rw.consumers(t)):
                 continue
-        op = ((hip_qkv_rope_cache, hip_qkv_rope_cache_s8),
-              (hip_qkv_rope_cache_rows, hip_qkv_rope_cache_rows_s8))[rows][sk[0] == "scaled"]
+        op = ((hip_qkv_rope_cache, hip_qkv_rope_cache_s8), (hip_qkv_rope_cache_rows, hip_qkv_rope_cache_rows_s8),
+              (hip_qkv_rope_cache_slots, hip_qkv_rope_cache_slots_s8))[rows + paged][sk[0] == "scaled"]
         rw.replace(at, op.bind(*b.args, *bufs, pos, output=(q, *outs)))
-        rw.drop(*({i, *sk[2], *sv[2], *at_copies} - {at}))
+        rw.drop(*({i, *sk[2], *sv[2], *at_copies, *links} - {at}))
+        flats |= flat_at
+    for j in flats:  # reshape(slots, -1) is shared by the layers of a step: it goes with its last reader
+        if all(rw.touched(c) for c in rw.consumers(rw.bsyms[j].output)):
+            rw.drop(j)
     return rw.finish(f"hipex: {rw.replaced} KV-cache write pair(s) fused into RoPE")
 
 
@@ -1265,6 +1374,73 @@ def _fuse_kv8_reads(trace):
                     break
                 rw.drop(j)
     return rw.finish(f"hipex: {rw.replaced} decode attention(s) read their e4m3 KV cache directly")
+
+
+def _paged_gather(rw, t):
+    """``(pool, table, page_size, position)`` when ``t = kv_paged_gather(pool, table, page_size)`` is read once,
+    else None."""
+    j = rw.producer(t)
+    if j is None or rw.touched(j) or rw.bsyms[j].sym.id not in _KV_PAGED_GATHER_IDS or rw.uses(t) != 1:
+        return None
+    p = operands(rw.bsyms[j], ("pool", "table", "page_size"))
+    if not all(isinstance(p[n], TensorProxy) for n in ("pool", "table")) or isinstance(p["page_size"], Proxy):
+        return None
+    return p["pool"], p["table"], p["page_size"], j
+
+
+def _fuse_kv_paged_reads(trace):
+    """``hip_decode_attn(q, kv_paged_gather(kp, table, page), kv_paged_gather(vp, table, page),
+    kv_paged_mask(pos, table, page, num_pages), False, scale)`` -> ``hip_decode_attn_paged(q, kp, vp, pos, table, page,
+    num_pages, scale)``: the kernel takes every key's pool row from the block table and every row's key count from its
+    position, so a decode step neither gathers the logical cache nor builds a mask.  The same over
+    ``hip_decode_attn_kv8`` / ``hip_decode_attn_kv8s``, whose byte (and scale) operands are gathers of the byte (and
+    scale) pools: ``hip_decode_attn_kv8_paged`` / ``hip_decode_attn_kv8s_paged``.
+
+    Every cache operand must be a gather read once, all at one table and page size, the mask a ``kv_paged_mask`` of
+    that table, page size and int64 ``pos`` ``[B, T]``, and ``causal`` false; nothing may write a pool in place
+    between its gather and the attention.  The gathers are dropped, and the mask with its last reader, when nothing
+    else reads it.  LTA_KV_PAGED_FUSION=0 turns the pass off."""
+    if _kv_paged_fusion_off():
+        return trace
+    rw = Rewrite(trace, ex)
+    forms = {hip_decode_attn: (hip_decode_attn_paged, ("k", "v")),
+             hip_decode_attn_kv8: (hip_decode_attn_kv8_paged, ("k8", "v8")),
+             hip_decode_attn_kv8s: (hip_decode_attn_kv8s_paged, ("k8", "v8", "k_scale", "v_scale"))}
+    masks = set()
+    for i, b in enumerate(rw.bsyms):
+        if b.sym not in forms or rw.touched(i):
+            continue
+        op, names = forms[b.sym]
+        p = operands(b)
+        q, mask = p["q"], p["mask"]
+        if p["causal"] or not isinstance(mask, TensorProxy):
+            continue
+        m = rw.producer(mask)
+        if m is None or rw.touched(m) or rw.bsyms[m].sym.id not in _KV_PAGED_MASK_IDS:
+            continue
+        pm = operands(rw.bsyms[m], ("pos", "table", "page_size", "num_pages"))
+        pos, table = pm["pos"], pm["table"]
+        if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or not isinstance(table, TensorProxy):
+            continue
+        if any(isinstance(pm[n], Proxy) for n in ("page_size", "num_pages")):
+            continue
+        if tuple(pos.shape) != (q.shape[0], q.shape[2]):
+            continue
+        gathers = [_paged_gather(rw, p[n]) if isinstance(p[n], TensorProxy) else None for n in names]
+        if any(g is None or g[1].name != table.name or g[2] != pm["page_size"] for g in gathers):
+            continue
+        # the kernel reads the pools where the attention stands: nothing may write them after their gather
+        if any(g[3] < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
+               for g in gathers for j in rw.consumers(g[0])):
+            continue
+        rw.replace(i, op.bind(q, *(g[0] for g in gathers), pos, table, pm["page_size"], pm["num_pages"], p["scale"],
+                              output=b.output))
+        rw.drop(*(g[3] for g in gathers))
+        masks.add(m)
+    for m in masks:  # one mask serves the layers of a step
+        if all(rw.touched(j) and not rw.dropped(j) for j in rw.consumers(rw.bsyms[m].output)):
+            rw.drop(m)
+    return rw.finish(f"hipex: {rw.replaced} decode attention(s) read their paged KV cache through the block table")
 
 
 def _fuse_rms_bwd_residual(trace):
@@ -1656,7 +1832,7 @@ _PASSES = (
     partial(_fuse_decode, kind=_MXFP4_DECODE, folds=("gate", "act", "residual", "norm", "group"),
             message="hipex: MXFP4 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
                     "{norm} norm prologue(s), {group} group(s))"),
-    _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv_position_reads, _fuse_kv8_reads,
+    _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv_position_reads, _fuse_kv8_reads, _fuse_kv_paged_reads,
     partial(_fuse_decode, kind=_BF16_DECODE, folds=("group",), message="hipex: {group} grouped decode projection launch(es)"),
     _fuse_qkv_rope_gemm, _fuse_fp8_qkv_rope_gemm, _fuse_attn_bwd_rope,
 )
@@ -2121,6 +2297,55 @@ hip_decode_attn_kv8_pos = ex.register_operator("hip_decode_attn_kv8_pos", meta=_
 hip_decode_attn_kv8s_pos = ex.register_operator(
     "hip_decode_attn_kv8s_pos", meta=lambda q, k8, v8, k_scale, v_scale, pos, scale: TensorProxy(like=q),
     fn=_decode_attn_kv8s_pos_impl)
+
+
+# The paged forms (ops/kv_pages.py): pools [Hkv, R + 1, D] read through the block table, key counts from ``pos``.
+def _decode_attn_paged_meta(q, k, v, pos, table, page_size, num_pages, scale):
+    return TensorProxy(like=q)
+
+
+def _paged_selector(caches, pos, table, page_size, num_pages):
+    """The operands of the mask form: every pool's logical cache and the paged mask."""
+    from ..ops.kv_pages import gather_pages, paged_mask
+
+    return [gather_pages(c, table, page_size) for c in caches], paged_mask(pos, table, page_size, num_pages)
+
+
+def _decode_attn_paged_impl(q, k, v, pos, table, page_size, num_pages, scale):
+    from ..ops.attention import decode_attn_paged, decode_attn_paged_supported
+
+    if decode_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
+        return decode_attn_paged(q, k, v, pos, table, page_size, num_pages, scale)
+    caches, mask = _paged_selector((k, v), pos, table, page_size, num_pages)
+    return _decode_attn_impl(q, *caches, mask, False, scale)
+
+
+def _decode_attn_kv8_paged_impl(q, k8, v8, pos, table, page_size, num_pages, scale):
+    from ..ops.attention import decode_attn_kv8_paged, decode_attn_kv8_paged_supported
+
+    if decode_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
+        return decode_attn_kv8_paged(q, k8, v8, pos, table, page_size, num_pages, scale)
+    caches, mask = _paged_selector((k8, v8), pos, table, page_size, num_pages)
+    return _decode_attn_kv8_impl(q, *caches, mask, False, scale)
+
+
+def _decode_attn_kv8s_paged_impl(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale):
+    from ..ops.attention import decode_attn_kv8s_paged, decode_attn_kv8s_paged_supported
+
+    if decode_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
+        return decode_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale)
+    caches, mask = _paged_selector((k8, v8, k_scale, v_scale), pos, table, page_size, num_pages)
+    return _decode_attn_kv8s_impl(q, *caches, mask, False, scale)
+
+
+hip_decode_attn_paged = ex.register_operator("hip_decode_attn_paged", meta=_decode_attn_paged_meta,
+                                             fn=_decode_attn_paged_impl)
+hip_decode_attn_kv8_paged = ex.register_operator("hip_decode_attn_kv8_paged", meta=_decode_attn_paged_meta,
+                                                 fn=_decode_attn_kv8_paged_impl)
+hip_decode_attn_kv8s_paged = ex.register_operator(
+    "hip_decode_attn_kv8s_paged",
+    meta=lambda q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale: TensorProxy(like=q),
+    fn=_decode_attn_kv8s_paged_impl)
 
 
 def _broadcastable(shape, target) -> bool:

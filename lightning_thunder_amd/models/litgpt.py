@@ -22,6 +22,7 @@ import torch.utils.checkpoint
 import torch.nn.functional as F
 
 from ..ops.kv8 import kv8_dequantise_rows, kv8_quantise_rows
+from ..ops.kv_pages import PageTable, check_page_size, kv_page_slots, kv_paged_gather, kv_paged_mask
 from ..ops.kv_rows import kv_position_mask
 
 
@@ -275,6 +276,76 @@ class KVCache(nn.Module):
             torch.nn.init.constant_(self.v_scale, 127)
 
 
+class PagedKVCache(nn.Module):
+    """Paged key/value cache (``ops/kv_pages.py``): pools ``[n_query_groups, num_pages * page_size + 1, head_size]``
+    whose rows are handed out in pages through the model's block table; the last row is the sink for tokens without
+    a page.  ``dtype`` and ``scale`` as :class:`KVCache` has them; the scale pools are
+    ``[n_query_groups, num_pages * page_size + 1, 1]``.
+
+    ``forward(slots, table, k, v)`` writes token (b, t) at pool row ``slots[b, t]`` and returns every sequence's
+    logical cache ``[B, n_query_groups, max_pages * page_size, head_size]``, dequantised as ``KVCache.forward``
+    does."""
+
+    def __init__(self, n_query_groups: int, head_size: int, page_size: int, num_pages: int, device=None, dtype=None,
+                 scale: Optional[str] = None):
+        super().__init__()
+        if scale not in (None, "row"):
+            raise ValueError(f"KV cache: scale must be None or 'row', got {scale!r}")
+        if scale is not None and dtype != torch.float8_e4m3fn:
+            raise ValueError(f"KV cache: scale={scale!r} needs dtype=torch.float8_e4m3fn, got {dtype}")
+        self.scale = scale
+        self.page_size = check_page_size(page_size)
+        self.num_pages = num_pages
+        if dtype == torch.float8_e4m3fn:
+            dtype = torch.uint8
+        elif dtype is not None and dtype.is_floating_point and dtype.itemsize == 1:
+            raise ValueError(f"KV cache: the only 8-bit float cache is torch.float8_e4m3fn, got {dtype}")
+        rows = num_pages * page_size + 1
+        self.register_buffer("k", torch.zeros((n_query_groups, rows, head_size), device=device, dtype=dtype),
+                             persistent=False)
+        self.register_buffer("v", torch.zeros((n_query_groups, rows, head_size), device=device, dtype=dtype),
+                             persistent=False)
+        if scale is not None:
+            for name in ("k_scale", "v_scale"):
+                self.register_buffer(name, torch.full((n_query_groups, rows, 1), 127, device=device, dtype=torch.uint8),
+                                     persistent=False)
+
+    def forward(self, slots: torch.Tensor, table: torch.Tensor, k: torch.Tensor, v: torch.Tensor):
+        B, H, T, _ = k.shape
+        flat = slots.reshape(-1)
+
+        def put(pool, src):  # [B, H, T, D] laid out as [H, B * T, D], one row per token
+            return pool.index_copy_(1, flat, src.permute(1, 0, 2, 3).reshape(H, B * T, src.shape[-1]))
+
+        def get(pool):
+            return kv_paged_gather(pool, table, self.page_size)
+
+        if self.scale is not None:
+            k8, ks = kv8_quantise_rows(k)
+            v8, vs = kv8_quantise_rows(v)
+            k_all, v_all = put(self.k, k8), put(self.v, v8)
+            ks_all, vs_all = put(self.k_scale, ks), put(self.v_scale, vs)
+            return (kv8_dequantise_rows(get(k_all), get(ks_all), k.dtype),
+                    kv8_dequantise_rows(get(v_all), get(vs_all), v.dtype))
+        if self.k.dtype == torch.uint8:
+            f8 = torch.float8_e4m3fn
+            k8 = k.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
+            v8 = v.clamp(-448.0, 448.0).to(f8).view(torch.uint8)
+            k_all, v_all = put(self.k, k8), put(self.v, v8)
+            return get(k_all).view(f8).to(k.dtype), get(v_all).view(f8).to(v.dtype)
+        return get(put(self.k, k.to(self.k.dtype))), get(put(self.v, v.to(self.v.dtype)))
+
+    def reset_parameters(self) -> None:
+        torch.nn.init.zeros_(self.k)
+        torch.nn.init.zeros_(self.v)
+        if self.scale is not None:
+            torch.nn.init.constant_(self.k_scale, 127)
+            torch.nn.init.constant_(self.v_scale, 127)
+
+    def nbytes(self) -> int:
+        return sum(b.numel() * b.element_size() for b in self.buffers())
+
+
 class CausalSelfAttention(nn.Module):
     def __init__(self, config: Config):
         super().__init__()
@@ -284,12 +355,15 @@ class CausalSelfAttention(nn.Module):
         self.kv_cache: Optional[KVCache] = None
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                input_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+                input_pos: Optional[torch.Tensor] = None, pages=None) -> torch.Tensor:
         B, T, C = x.shape
         c = self.config
         qkv = self.attn(x)
         q, k, v = qkv_split_rope(qkv, cos, sin, c.n_head, c.n_query_groups, c.head_size, c.rope_n_elem)
-        if input_pos is not None:
+        if pages is not None:  # a paged cache: (slots [B, T], the block table), computed once per step by GPT.forward
+            k, v = self.kv_cache(pages[0], pages[1], k, v)
+            y = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, enable_gqa=c.n_query_groups != c.n_head)
+        elif input_pos is not None:
             if self.kv_cache is None:
                 raise TypeError("call model.set_kv_cache(...) before passing input_pos")
             k, v = self.kv_cache(input_pos, k, v)
@@ -404,9 +478,10 @@ class Block(nn.Module):
         self.config = config
 
     def forward(self, x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, mask: Optional[torch.Tensor] = None,
-                input_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
+                input_pos: Optional[torch.Tensor] = None, pages=None) -> torch.Tensor:
         x_normed = self.norm_1(x)
-        h = self.attn(x_normed, cos, sin, mask, input_pos)
+        h = self.attn(x_normed, cos, sin, mask, input_pos) if pages is None else \
+            self.attn(x_normed, cos, sin, mask, input_pos, pages)
         if self.config.parallel_residual:
             n2 = x_normed if self.norm_2 is None else self.norm_2(x)
             return self.mlp(n2) + h + x
@@ -433,6 +508,8 @@ class GPT(nn.Module):
         self.register_buffer("cos", torch.empty(0), persistent=False)
         self.register_buffer("sin", torch.empty(0), persistent=False)
         self.mask_cache: Optional[torch.Tensor] = None
+        self.kv_pages: Optional[PageTable] = None  # the allocator of a paged KV cache (set_kv_cache(page_size=...))
+        self.page_table: Optional[torch.Tensor] = None  # its device block table, shared by all layers
         self._rope_seq = 0
 
     def set_rope_cache(self, seq_len: int, device=None) -> None:
@@ -443,18 +520,45 @@ class GPT(nn.Module):
         self._rope_seq = seq_len
 
     def set_kv_cache(self, batch_size: int, max_seq_length: Optional[int] = None, device=None,
-                     dtype: Optional[torch.dtype] = None, scale: Optional[str] = None) -> None:
+                     dtype: Optional[torch.dtype] = None, scale: Optional[str] = None,
+                     page_size: Optional[int] = None, num_pages: Optional[int] = None) -> None:
         """Allocates a static KV cache in every block and the causal mask for incremental decoding.
         ``dtype=torch.float8_e4m3fn`` stores the caches as unscaled, saturating e4m3 in ``uint8`` buffers
         (see :class:`KVCache`); any other 8-bit float dtype raises ``ValueError``.  ``scale="row"`` with
         that dtype adds one power-of-two scale byte per (token, kv head) row; with any other dtype it
-        raises ``ValueError``."""
+        raises ``ValueError``.
+
+        ``page_size`` (a power of two >= 16, else ``ValueError``) makes the cache a paged one (``ops/kv_pages.py``):
+        every block gets a :class:`PagedKVCache` of ``num_pages`` pages (default ``batch_size * max_pages``, what
+        the static cache would hold) in the same ``dtype`` / ``scale`` formats, the model gets the allocator
+        ``self.kv_pages`` with ``max_pages = ceil(max_seq_length / page_size)`` table entries per sequence, and
+        ``self.max_seq_length`` becomes ``max_pages * page_size``.  Such a model takes the 2-D ``input_pos`` only."""
         if scale is not None and dtype != torch.float8_e4m3fn:
             raise ValueError(f"set_kv_cache: scale={scale!r} needs dtype=torch.float8_e4m3fn, got {dtype}")
         c = self.config
         max_seq_length = max_seq_length or c.block_size
         dtype = dtype or self.lm_head.weight.dtype
         device = device or self.lm_head.weight.device
+        if page_size is None:
+            if num_pages is not None:
+                raise ValueError("set_kv_cache: num_pages needs a page_size")
+            self.kv_pages = self.page_table = None
+        else:
+            check_page_size(page_size)
+            max_pages = -(-max_seq_length // page_size)
+            num_pages = batch_size * max_pages if num_pages is None else num_pages
+            self.kv_pages = PageTable(batch_size, max_pages, page_size, num_pages, device=device)
+            self.page_table = self.kv_pages.table
+            for block in self.transformer.h:
+                ac = getattr(block.attn, "config", c)
+                block.attn.kv_cache = PagedKVCache(ac.n_query_groups, ac.head_size, page_size, num_pages, device=device,
+                                                   dtype=dtype, scale=scale)
+            max_seq_length = max_pages * page_size
+            if self.cos.numel() == 0 or self.cos.shape[0] < max_seq_length:
+                self.set_rope_cache(max_seq_length, device=device)
+            self.mask_cache = None
+            self.max_seq_length = max_seq_length
+            return
         for block in self.transformer.h:
             # sized from the attention module's own config: under head-parallel TP it holds only
             # this rank's kv groups (distributed/tensor_parallel swaps in a localized config)
@@ -471,12 +575,27 @@ class GPT(nn.Module):
         for block in self.transformer.h:
             block.attn.kv_cache = None
         self.mask_cache = None
+        self.kv_pages = self.page_table = None
 
     def forward(self, idx: torch.Tensor, input_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
         T = idx.size(1)
         if self.cos.numel() == 0 or self.cos.shape[0] < T:
             raise RuntimeError("call model.set_rope_cache(seq_len, device) before forward")
-        if input_pos is not None and input_pos.dim() == 2:  # a ragged batch: one position per (sequence, token)
+        pages = None
+        if input_pos is not None and self.kv_pages is not None:  # a paged cache: slots and mask once per step
+            if input_pos.dim() != 2:
+                raise TypeError("a paged KV cache takes the 2-D input_pos [B, T] (one position per token) only, "
+                                f"got {input_pos.dim()}-D")
+            B = idx.size(0)
+            flat = input_pos.reshape(-1)
+            cos = self.cos.index_select(0, flat).view(B, T, -1)
+            sin = self.sin.index_select(0, flat).view(B, T, -1)
+            pt = self.kv_pages
+            table = self.page_table
+            slots = kv_page_slots(table, input_pos, pt.page_size, pt.num_pages * pt.page_size)
+            mask = kv_paged_mask(input_pos, table, pt.page_size, pt.num_pages)
+            pages = (slots, table)
+        elif input_pos is not None and input_pos.dim() == 2:  # a ragged batch: one position per (sequence, token)
             B = idx.size(0)
             flat = input_pos.reshape(-1)
             cos = self.cos.index_select(0, flat).view(B, T, -1)
@@ -498,6 +617,8 @@ class GPT(nn.Module):
                 # recompute the block's intermediates in the backward (LitGPT / benchmark_litgpt
                 # ``--checkpoint_activations``); traced as ltorch.checkpoint
                 x = torch.utils.checkpoint.checkpoint(block, x, cos, sin, mask, None, use_reentrant=False)
+            elif pages is not None:
+                x = block(x, cos, sin, mask, input_pos, pages)
             else:
                 x = block(x, cos, sin, mask, input_pos)
         x = self.transformer.ln_f(x)
@@ -563,6 +684,8 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
     from ..ops.sampling import argmax_last, sample_last
 
     forward = forward or model
+    if prompt_lengths is None and getattr(model, "kv_pages", None) is not None:  # a paged cache: always the ragged route
+        prompt_lengths = torch.full((prompt.shape[0],), prompt.shape[1], device=prompt.device, dtype=torch.int64)
     if prompt_lengths is not None:
         return _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k, top_p, eos_id,
                                 prompt_lengths, pad_id)
@@ -599,7 +722,11 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
     ``logits[b, len_b - 1]``.  Every decode step feeds ``[B, 1]`` tokens with one int64 ``[B, 1]`` position
     tensor that starts at ``prompt_lengths`` and is advanced in place (fixed addresses: a hipGraph replays).
     A sequence that has produced ``eos_id`` keeps riding in the batch, its later tokens are ``pad_id``; the
-    loop ends when all are done.  Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
+    loop ends when all are done.
+
+    On a paged cache (``set_kv_cache(page_size=...)``) the prefill runs at ``arange(Tmax)`` expanded to ``[B, Tmax]``
+    after ``model.kv_pages.reserve(prompt_lengths)``, and before every decode step the sequences that are not
+    finished get room for one more token, from host-side counters; a finished sequence receives no further page.  Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
     from column ``len_b`` on, then ``pad_id``."""
     from ..ops.sampling import argmax_last, sample_last
 
@@ -614,15 +741,25 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
     lo, hi = int(lengths.min()), int(lengths.max())
     if lo < 1 or hi > T:
         raise ValueError(f"generate: prompt_lengths must lie in [1, {T}], got {lo} .. {hi}")
-    if hi + max_new_tokens > cache.k.shape[2]:
+    pages = getattr(model, "kv_pages", None)
+    capacity = cache.k.shape[2] if pages is None else pages.capacity
+    if hi + max_new_tokens > capacity:
         raise ValueError(f"generate: the longest prompt ({hi}) plus {max_new_tokens} new tokens exceeds the KV "
-                         f"cache of {cache.k.shape[2]} positions")
+                         f"cache of {capacity} positions")
     out = torch.full((B, T + max_new_tokens), pad_id, device=device, dtype=prompt.dtype)
     cols = torch.arange(T, device=device)
     out[:, :T] = torch.where(cols[None, :] < lengths[:, None], prompt, torch.full_like(prompt, pad_id))
     if max_new_tokens <= 0:
         return out
-    logits = forward(prompt, torch.arange(T, device=device))
+    if pages is None:
+        logits = forward(prompt, torch.arange(T, device=device))
+    else:
+        # pages for the prompts; a pad token beyond its sequence's last page has no slot and falls to the sink row
+        held = lengths.tolist()  # host-side counters from here on
+        live = [True] * B
+        pages.reset()  # a generation starts from an empty table, as it overwrites a static cache
+        pages.reserve(held)
+        logits = forward(prompt, torch.arange(T, device=device).expand(B, T).contiguous())
     last = logits[torch.arange(B, device=device), lengths - 1]
     pos = lengths.clone().view(B, 1)  # where the next token of every sequence goes; advanced in place
     done = torch.zeros(B, 1, device=device, dtype=torch.bool)
@@ -637,7 +774,12 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
             done = done | (nxt == eos_id)
             if bool(done.all()):
                 break
+            if pages is not None:
+                live = [not d for d in done.view(-1).tolist()]
         if i + 1 < max_new_tokens:
+            if pages is not None:  # room for this step's token; a finished sequence gets no further page
+                held = [n + 1 if alive else n for n, alive in zip(held, live)]
+                pages.reserve(held)
             logits = forward(nxt, pos)
             last = logits[:, -1]
             pos.add_(1)

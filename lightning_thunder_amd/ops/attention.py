@@ -385,6 +385,8 @@ for _entry, _scale_ptrs in (("lta_decode_attn", 0), ("lta_decode_attn_kv8", 0), 
     _head = [c_int, *[c_void_p] * (7 + _scale_ptrs), *[c_int] * 6, c_void_p]
     register_signature(_entry, [*_head, c_int, c_int, c_int, c_float, c_int, c_void_p])
     register_signature(_entry + "_pos", [*_head, c_int, c_float, c_int, c_void_p])
+    # the paged entries: the position entries', then the block table, log2 of the page size and the page count
+    register_signature(_entry + "_paged", [*_head, c_int, c_float, c_int, c_void_p, c_int, c_int, c_void_p])
 
 DECODE_MAX_QUERIES = 16
 
@@ -402,17 +404,30 @@ def decode_launch_shape(rows: int, S: int):
     return wsplit, nsplit, chunk
 
 
-def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: bool = False, pos=None, scales=()):
+def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: bool = False, pos=None, scales=(),
+                   pages=None):
     """One launch of ``entry``: a mask entry with (``mask``, ``causal``), a position entry with ``pos``.  ``scales`` =
     (k_scale, v_scale) for the scaled-e4m3 entries, whose argument list carries the two pointers after v.  The
     stride record is q, k, v (b, h, t each), then the selector's (mask b, h, t, s or pos b, t), then the scales'.
+
+    ``pages`` = (table, page_size, num_pages) for the paged entries (``ops/kv_pages.py``): k / v (and the scales) are
+    pools ``[Hkv, R + 1, D]`` whose batch stride goes on as 0, ``S`` is the table's logical capacity, the table's two
+    strides end the stride record, and the table, log2(page_size) and num_pages follow ``wsplit``.
 
     The grid comes from the capacity S in both modes (``decode_launch_shape``): positions stay on the device, so a
     hipGraph replays the launch while they advance; the kernel splits each row's live range over the ``nsplit``
     workgroups itself."""
     lib = require()
     B, Hq, T, D = q.shape
-    Hkv, S = k.shape[1], k.shape[2]
+    if pages is not None:
+        table, page_size, num_pages = pages
+        Hkv, S = k.shape[0], table.shape[1] * page_size
+        cache_st = lambda c: (0, *c.stride()[:2])
+        tail = (*table.stride(), ptr(table), page_size.bit_length() - 1, num_pages)
+    else:
+        Hkv, S = k.shape[1], k.shape[2]
+        cache_st = lambda c: c.stride()[:3]
+        tail = ()
     sc = scale if scale is not None else 1.0 / math.sqrt(D)
     rows = B * Hq * T
     wsplit, nsplit, chunk = decode_launch_shape(rows, S)
@@ -426,11 +441,11 @@ def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: 
     else:
         sel = mask if mask is None else torch.broadcast_to(mask, (B, Hq, T, S))
         sel_st, split = (0, 0, 0, 0) if mask is None else sel.stride(), (chunk, nsplit, int(causal))
-    st = (*q.stride()[:3], *k.stride()[:3], *v.stride()[:3], *sel_st, *(s for c in scales for s in c.stride()[:3]))
+    st = (*q.stride()[:3], *cache_st(k), *cache_st(v), *sel_st, *(s for c in scales for s in cache_st(c)), *tail[:2])
     st = (ctypes.c_int64 * len(st))(*st)
     rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *map(ptr, scales), ptr(sel), ptr(o), ptr(ws_acc),
                              ptr(ws_ml), B, Hq, Hkv, T, S, D, ctypes.cast(st, ctypes.c_void_p), *split, float(sc),
-                             int(wsplit), stream_ptr(q.device))
+                             int(wsplit), *tail[2:], stream_ptr(q.device))
     check(rc, entry)
     return o
 
@@ -547,3 +562,77 @@ def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None =
         raise _refusal("decode_attn_kv8s_pos", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos)
     return _decode_launch("lta_decode_attn_kv8s_pos", *_e4m3_in_place(q, k8, v8), scale, pos=pos,
                           scales=(k_scale, v_scale))
+
+
+# ------------------------------------------------------------------------------------------------
+# Paged mode of the decode kernels (ops/kv_pages.py): the position mode with every key's row taken from a block table
+# ------------------------------------------------------------------------------------------------
+def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=()) -> bool:
+    """16-bit q [B, Hq, T, D] with D 64 / 128 and at most DECODE_MAX_QUERIES rows; pools k / v [Hkv, rows, D] of
+    ``cache_dtype`` read in place (head dim contiguous, 16-byte aligned rows and heads) with Hkv dividing Hq and
+    ``rows >= num_pages * page_size``; scale pools uint8 [Hkv, rows, 1]; int64 ``pos`` [B, T] and ``table``
+    [B, max_pages >= 1] on q's device; ``page_size`` a power of two >= 16 and ``num_pages`` >= 1, both ints."""
+    if not all(isinstance(n, int) and not isinstance(n, bool) for n in (page_size, num_pages)):
+        return False
+    if page_size < 16 or page_size & (page_size - 1) or num_pages < 1 or num_pages * page_size >= 2 ** 31:
+        return False
+    if not (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
+            and 0 < q.shape[2] <= DECODE_MAX_QUERIES):
+        return False
+    unit = 16 // k.element_size()  # elements per 16 bytes
+    for c in (k, v):
+        if c.dtype != cache_dtype or c.dim() != 3 or c.shape != k.shape or c.device != q.device:
+            return False
+        if c.stride(2) != 1 or c.stride(0) % unit or c.stride(1) % unit or c.data_ptr() % 16:
+            return False
+    Hkv, rows, D = k.shape
+    if D != q.shape[-1] or Hkv < 1 or q.shape[1] % Hkv or rows < num_pages * page_size:
+        return False
+    if any(s is None or s.dtype != torch.uint8 or s.device != q.device or tuple(s.shape) != (Hkv, rows, 1)
+           for s in scales):
+        return False
+    return all(t is not None and t.dtype == torch.int64 and t.dim() == 2 and t.device == q.device
+               and t.shape[0] == q.shape[0] for t in (pos, table)) and pos.shape[1] == q.shape[2] \
+        and table.shape[1] >= 1 and table.shape[1] * page_size < 2 ** 31
+
+
+def decode_attn_paged_supported(q, k, v, pos, table, page_size, num_pages) -> bool:
+    """What the 16-bit paged kernel takes: see ``_paged_ok``, with pools of q's dtype."""
+    return _paged_ok(q, k, v, pos, table, page_size, num_pages, q.dtype)
+
+
+def decode_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages) -> bool:
+    return _paged_ok(q, k8, v8, pos, table, page_size, num_pages, torch.uint8)
+
+
+def decode_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages) -> bool:
+    return _paged_ok(q, k8, v8, pos, table, page_size, num_pages, torch.uint8, (k_scale, v_scale))
+
+
+def decode_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+    """``decode_attn_pos`` over a paged cache: k / v pools ``[Hkv, R + 1, D]``, ``table`` int64 ``[B, max_pages]``.
+    Row (b, hq, t) attends the keys ``j <= pos[b, t]`` (clamped to the capacity ``S = max_pages * page_size``) whose
+    table entry lies in ``[0, num_pages)``, each read at pool row ``table[b, j // page_size] * page_size + j %
+    page_size``: what ``decode_attn`` computes over ``gather_pages`` under ``paged_mask``.  No key gives a NaN row."""
+    if not decode_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
+        raise _refusal("decode_attn_paged", q=q, k=k, v=v, pos=pos, table=table)
+    return _decode_launch("lta_decode_attn_paged", _rows_in_place(q), k, v, scale, pos=pos,
+                          pages=(table, page_size, num_pages))
+
+
+def decode_attn_kv8_paged(q, k8, v8, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+    """``decode_attn_paged`` over unscaled e4m3 pools (uint8)."""
+    if not decode_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
+        raise _refusal("decode_attn_kv8_paged", q=q, k=k8, v=v8, pos=pos, table=table)
+    return _decode_launch("lta_decode_attn_kv8_paged", _rows_in_place(q), k8, v8, scale, pos=pos,
+                          pages=(table, page_size, num_pages))
+
+
+def decode_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size: int, num_pages: int,
+                           scale: float | None = None):
+    """``decode_attn_paged`` over the scaled e4m3 pools: bytes ``[Hkv, R + 1, D]`` and scale bytes ``[Hkv, R + 1, 1]``."""
+    if not decode_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
+        raise _refusal("decode_attn_kv8s_paged", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos,
+                       table=table)
+    return _decode_launch("lta_decode_attn_kv8s_paged", _rows_in_place(q), k8, v8, scale, pos=pos,
+                          scales=(k_scale, v_scale), pages=(table, page_size, num_pages))

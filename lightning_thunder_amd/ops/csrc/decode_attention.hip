@@ -78,6 +78,23 @@ struct RowPos {
 };
 struct NoPos {};
 
+// Paged mode (PAGED, a position mode): k / v are pools [Hkv, R + 1, D] of pages of 2^lg_page rows and key j of
+// sequence b sits at pool row table[b, j >> lg_page] * 2^lg_page + (j & (2^lg_page - 1)) (ops/kv_pages.py; the
+// scale bytes at the same row).  Strides of the int64 table in elements over b and the page index.  A key whose
+// table entry is outside [0, num_pages) is invalid exactly like a masked key: nothing of it is loaded, so a bad
+// entry never reads outside the pool, and a 64-key block without a valid key is skipped before any K / V traffic.
+// The row's live range, its split over gridDim.y, the softmax and the combine are the position mode's.
+struct PageMap {
+  const int64_t* table;
+  int64_t sb, sp;
+  int lg_page, num_pages;
+};
+struct PagedPos : RowPos {
+  PageMap pg;
+};
+template <bool POS, bool PAGED>
+using Selector = std::conditional_t<PAGED, PagedPos, std::conditional_t<POS, RowPos, NoPos>>;
+
 // KS (with KV = uint8_t): the cache is the scaled one.  The lane that owns key j loads that key's two scale
 // bytes (consecutive bytes across the lanes of a 64-key block) and forms 2^e as byte << 23; the score is
 // dot * 2^ek and V is accumulated with p * 2^ev in place of p, while l keeps the unscaled p.  Both products
@@ -95,14 +112,15 @@ struct NoPos {};
 // under an all-true mask bit for bit.  `mask`, `chunk` and `causal` are unused.  All three position kernels
 // round acc / l as the 16-bit kernel does (`normalised` with its scaled-cache form), so both e4m3 ones equal
 // the 16-bit one over the dequantised cache bit for bit, with the exclusions above (a zero result's sign included).
-template <typename T, typename KV, int D, bool WSPLIT, bool KS = false, bool POS = false>
+template <typename T, typename KV, int D, bool WSPLIT, bool KS = false, bool POS = false, bool PAGED = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const T* __restrict__ q, const KV* __restrict__ k, const KV* __restrict__ v, const uint8_t* __restrict__ mask,
     T* __restrict__ o, float* __restrict__ ws_acc, float* __restrict__ ws_ml, int B, int Hq, int Hkv, int Tq, int S,
     int64_t qsb, int64_t qsh, int64_t qst, int64_t ksb, int64_t ksh, int64_t kss, int64_t vsb, int64_t vsh,
     int64_t vss, int64_t msb, int64_t msh, int64_t mst, int64_t mss, int chunk, int causal, float scale,
-    std::conditional_t<KS, KVScales, NoScales> sc, std::conditional_t<POS, RowPos, NoPos> rp) {
+    std::conditional_t<KS, KVScales, NoScales> sc, Selector<POS, PAGED> rp) {
   static_assert(!KS || sizeof(KV) == 1, "scales belong to an e4m3 cache");
+  static_assert(!PAGED || POS, "a paged cache is read by positions");
   constexpr int DPL = D / 64;          // output dims per lane after the final reduce-scatter
   constexpr bool kE4M3 = sizeof(KV) == 1;
   constexpr int NV = 16 / sizeof(KV);  // elements per 16-byte load
@@ -157,16 +175,24 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     if constexpr (!POS) {
       if (valid && mrow) valid = mrow[(int64_t)j * mss] != 0;
     }
+    [[maybe_unused]] int64_t r = j;  // the key's row in its cache
+    if constexpr (PAGED) {
+      if (valid) {  // one table entry per lane: j < j_end <= S = (table entries per sequence) << lg_page
+        const int64_t pid = rp.pg.table[b * rp.pg.sb + (int64_t)(j >> rp.pg.lg_page) * rp.pg.sp];
+        valid = pid >= 0 && pid < rp.pg.num_pages;
+        r = (pid << rp.pg.lg_page) + (j & ((1 << rp.pg.lg_page) - 1));
+      }
+    }
     if (!__any(valid)) continue;  // fully masked block: no K/V traffic
     float s = -INFINITY;
     // scale bytes of key j's K row and V row: loaded ahead of the K row, turned into 2^e where first used
     [[maybe_unused]] uint32_t kb = 127, vb = 127;
     if (valid) {
       if constexpr (KS) {
-        kb = ksrow[(int64_t)j * sc.kss];
-        vb = vsrow[(int64_t)j * sc.vss];
+        kb = ksrow[(PAGED ? r : (int64_t)j) * sc.kss];
+        vb = vsrow[(PAGED ? r : (int64_t)j) * sc.vss];
       }
-      const KV* krow = kbase + (int64_t)j * kss;
+      const KV* krow = kbase + (PAGED ? r : (int64_t)j) * kss;
       float dot = 0.f;
 #pragma unroll
       for (int d = 0; d < D; d += NV) {
@@ -190,7 +216,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     l = l * corr + wave_sum(p);
     m = m_new;
     if (valid) {
-      const KV* vrow = vbase + (int64_t)j * vss;
+      const KV* vrow = vbase + (PAGED ? r : (int64_t)j) * vss;
       const float pv = KS ? p * __uint_as_float(vb << 23) : p;
 #pragma unroll
       for (int d = 0; d < D; d += NV) {
@@ -295,20 +321,20 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
 }
 
-template <typename T, typename KV, int D, bool KS = false, bool POS = false>
+template <typename T, typename KV, int D, bool KS = false, bool POS = false, bool PAGED = false>
 int launch(const void* q, const void* k, const void* v, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
            int Hq, int Hkv, int Tq, int S, const int64_t* st, int chunk, int nsplit, int causal, float scale,
            int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc = {},
-           std::conditional_t<POS, RowPos, NoPos> rp = {}) {
+           Selector<POS, PAGED> rp = {}) {
   const int rows = B * Tq * Hq;
   if (wsplit) {
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS, POS>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS, POS, PAGED>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
                        (const KV*)k, (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
                        Tq, S, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11],
                        st[12], chunk, causal, scale, sc, rp);
   } else {
     dim3 grid((rows + kRowsPerBlock - 1) / kRowsPerBlock, nsplit);
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS, POS>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS, POS, PAGED>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
                        (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
                        st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12],
                        chunk, causal, scale, sc, rp);
@@ -320,14 +346,14 @@ int launch(const void* q, const void* k, const void* v, const void* mask, void* 
 }
 
 // `launch` for q / o of `dtype` and head dim D; KV = void: the cache holds q's type.  `a`: launch's arguments.
-template <typename KV, bool KS = false, bool POS = false, typename... A>
+template <typename KV, bool KS = false, bool POS = false, bool PAGED = false, typename... A>
 int dispatch(int dtype, int D, A... a) {
   using B16 = __hip_bfloat16;
   constexpr bool kSame = std::is_void_v<KV>;
-  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, POS>(a...);
-  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, POS>(a...);
-  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, POS>(a...);
-  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, POS>(a...);
+  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, POS, PAGED>(a...);
+  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, POS, PAGED>(a...);
+  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, POS, PAGED>(a...);
+  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, POS, PAGED>(a...);
   return (int)hipErrorInvalidValue;
 }
 
@@ -346,10 +372,13 @@ bool e4m3_cache_ok(const void* k, const void* v, const int64_t* strides) {
 //   q b,h,t | k b,h,s | v b,h,s | the selector's | with KS: k scale b,h,s | v scale b,h,s (bytes),
 // where the selector `sel` is the bool mask (strides b,h,t,s; may be null) or, with POS, the int64 positions
 // [B, Tq] (strides b,t; see RowPos).  KV = void: the cache holds q's type; uint8_t: e4m3.
-template <typename KV, bool KS, bool POS>
+// PAGED: k / v (and the scales) are pools, their b strides 0 and S the logical capacity, a multiple of the page;
+// `table` int64 [B, S >> lg_page] with its strides b,p last in `strides`; see PageMap.
+template <typename KV, bool KS, bool POS, bool PAGED = false>
 int decode_entry(int dtype, const void* q, const void* k, const void* v, const void* k_scale, const void* v_scale,
                  const void* sel, void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
-                 const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit, void* stream) {
+                 const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit, void* stream,
+                 const void* table = nullptr, int lg_page = 0, int num_pages = 0) {
   constexpr int kSel = POS ? 2 : 4;  // strides of the selector; the scales' follow them
   if (!sizes_ok(Hq, Hkv, POS ? 64 : chunk, nsplit)) return (int)hipErrorInvalidValue;  // POS: no chunk to check
   if (nsplit > 1 && (ws_acc == nullptr || ws_ml == nullptr)) return (int)hipErrorInvalidValue;
@@ -363,12 +392,21 @@ int decode_entry(int dtype, const void* q, const void* k, const void* v, const v
     const int64_t* ss = strides + 9 + kSel;
     sc = KVScales{(const uint8_t*)k_scale, (const uint8_t*)v_scale, ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]};
   }
-  std::conditional_t<POS, RowPos, NoPos> rp{};
+  Selector<POS, PAGED> rp{};
   if constexpr (POS) {
     if (sel == nullptr || S < 0) return (int)hipErrorInvalidValue;
-    rp = RowPos{(const int64_t*)sel, strides[9], strides[10]};
+    rp.pos = (const int64_t*)sel;
+    rp.sb = strides[9];
+    rp.st = strides[10];
   }
-  return dispatch<KV, KS, POS>(dtype, D, q, k, v, POS ? (const void*)nullptr : sel, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
+  if constexpr (PAGED) {
+    if (table == nullptr || lg_page < 4 || lg_page > 24 || num_pages <= 0 || num_pages > (INT32_MAX >> lg_page) ||
+        S % (1 << lg_page))
+      return (int)hipErrorInvalidValue;
+    const int64_t* ts = strides + 9 + kSel + (KS ? 6 : 0);
+    rp.pg = PageMap{(const int64_t*)table, ts[0], ts[1], lg_page, num_pages};
+  }
+  return dispatch<KV, KS, POS, PAGED>(dtype, D, q, k, v, POS ? (const void*)nullptr : sel, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
                                (const int64_t*)st, chunk, nsplit, causal, scale, wsplit, (hipStream_t)stream, sc, rp);
 }
 
@@ -427,4 +465,34 @@ LTA_EXPORT int lta_decode_attn_kv8s_pos(int dtype, const void* q, const void* k,
                                         float scale, int wsplit, void* stream) {
   return lta::decode_entry<uint8_t, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, ws_acc, ws_ml, B, Hq, Hkv, Tq,
                                                 S, D, strides, 0, nsplit, 0, scale, wsplit, stream);
+}
+
+// The paged entries: the position entries over a paged cache (ops/kv_pages.py).  k / v are pools [Hkv, R + 1, D]
+// (strides b = 0, h, row), `table` int64 [B, S >> lg_page], S the logical capacity; see PageMap.
+LTA_EXPORT int lta_decode_attn_paged(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o,
+                                     void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                     const int64_t* strides, int nsplit, float scale, int wsplit, const void* table,
+                                     int lg_page, int num_pages, void* stream) {
+  return lta::decode_entry<void, false, true, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B, Hq, Hkv,
+                                                    Tq, S, D, strides, 0, nsplit, 0, scale, wsplit, stream, table,
+                                                    lg_page, num_pages);
+}
+
+LTA_EXPORT int lta_decode_attn_kv8_paged(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                         void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S,
+                                         int D, const int64_t* strides, int nsplit, float scale, int wsplit,
+                                         const void* table, int lg_page, int num_pages, void* stream) {
+  return lta::decode_entry<uint8_t, false, true, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B, Hq,
+                                                       Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit, stream,
+                                                       table, lg_page, num_pages);
+}
+
+LTA_EXPORT int lta_decode_attn_kv8s_paged(int dtype, const void* q, const void* k, const void* v, const void* k_scale,
+                                          const void* v_scale, const void* pos, void* o, void* ws_acc, void* ws_ml,
+                                          int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
+                                          int nsplit, float scale, int wsplit, const void* table, int lg_page,
+                                          int num_pages, void* stream) {
+  return lta::decode_entry<uint8_t, true, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, ws_acc, ws_ml, B, Hq,
+                                                      Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit, stream,
+                                                      table, lg_page, num_pages);
 }

@@ -88,10 +88,12 @@ def qkv_rope_cache_scaled_supported(qkv, kc, vc, k_scale, v_scale, pos, n_query_
             and scale_caches_of((k_scale, v_scale), (kc, vc)))
 
 
-def _qkv_rope_cache_launch(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, caches, pos, suffix="", *capacity):
+def _qkv_rope_cache_launch(qkv, cos, sin, n_head, n_query_groups, head_size, rope_n, caches, pos, suffix="", *capacity,
+                           pooled: bool = False):
     """One launch of the cache-writing entry for ``caches`` = (kc, vc) or (kc, vc, k_scale, v_scale), over contiguous
     qkv / cos / sin / pos; the per-row entries have the ``suffix`` "_rows" and take the caches' ``capacity`` after
-    rope_n.  Returns (q, *caches)."""
+    rope_n.  ``pooled``: the caches are the ``[ng, rows, hs]`` pools of a paged cache, shared by the batch (batch
+    stride 0).  Returns (q, *caches)."""
     lib = require()
     B, T, _ = qkv.shape
     if cos.dtype != sin.dtype:
@@ -99,7 +101,8 @@ def _qkv_rope_cache_launch(qkv, cos, sin, n_head, n_query_groups, head_size, rop
     if cos.dtype not in (torch.float32, qkv.dtype):
         cos, sin = cos.float(), sin.float()
     q = torch.empty((B, n_head, T, head_size), device=qkv.device, dtype=qkv.dtype)
-    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches for s in c.stride()[:3]))
+    st = (ctypes.c_int64 * (3 * len(caches)))(*(s for c in caches
+                                                for s in ((0, *c.stride()[:2]) if pooled else c.stride()[:3])))
     entry = ("lta_qkv_rope_cache_fwd" + ("_kv8s" if len(caches) == 4 else "_kv8" if caches[0].dtype == torch.uint8 else "")
              + suffix)
     rc = getattr(lib, entry)(dcode(qkv), dcode(cos), ptr(qkv), ptr(cos), ptr(sin), ptr(q), *map(ptr, caches), ptr(pos),
@@ -165,6 +168,55 @@ def qkv_rope_cache_rows_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, hea
     scales = () if k_scale is None else (k_scale, v_scale)
     return _qkv_rope_cache_launch(_c(qkv), _c(cos), _c(sin), n_head, n_query_groups, head_size, rope_n,
                                   (kc, vc, *scales), _c(pos), "_rows", kc.shape[2])
+
+
+def qkv_rope_cache_slots_supported(qkv, cos, sin, kp, vp, slots, n_query_groups: int, head_size: int,
+                                   rope_n: int | None = None, k_scale=None, v_scale=None) -> bool:
+    """``qkv_rope_cache_rows_supported`` for the pools of a paged cache (``ops/kv_pages.py``): kp / vp
+    ``[ng, R + 1, hs]`` under the same dtype, layout and alignment rules, scale pools uint8 ``[ng, R + 1, 1]``, one
+    int64 pool row per token ``slots`` ``[B, T]`` and cos / sin ``[B, T, rope_n]``."""
+    if (k_scale is None) != (v_scale is None) or qkv.dim() != 3 or slots.dim() != 2:
+        return False
+    B, T, _ = qkv.shape
+    rn = head_size if rope_n is None else rope_n
+    if B == 0 or slots.dtype != torch.int64 or tuple(slots.shape) != (B, T) or slots.device != qkv.device:
+        return False
+    if head_size % 8 or rn % 16 or rn > head_size:
+        return False
+    if any(t.dim() != 3 or tuple(t.shape) != (B, T, rn) or not t.is_floating_point() for t in (cos, sin)):
+        return False
+    kv8 = kp.dtype == torch.uint8 and vp.dtype == torch.uint8
+    if kv8 and not _row_kernel_shape(qkv.dtype, head_size, rn):
+        return False
+    if kp.dim() != 3 or vp.dim() != 3 or kp.shape[1] != vp.shape[1] or kp.shape[1] < 1:  # one capacity bounds every write
+        return False
+    for c in (kp, vp):
+        if c.dtype != (torch.uint8 if kv8 else qkv.dtype) or c.device != qkv.device:
+            return False
+        if c.shape[0] != n_query_groups or c.shape[2] != head_size:
+            return False
+        if c.stride(2) != 1 or any(st % 8 for st in c.stride()[:2]) or c.data_ptr() % (8 if kv8 else 16):
+            return False
+    if k_scale is None:
+        return True
+    return kv8 and head_size <= 1024 and all(
+        s.dtype == torch.uint8 and s.device == qkv.device and tuple(s.shape) == (n_query_groups, kp.shape[1], 1)
+        for s in (k_scale, v_scale))
+
+
+def qkv_rope_cache_slots_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int, kp, vp,
+                             slots, k_scale=None, v_scale=None):
+    """``qkv_rope_cache_rows_fwd`` into the pools of a paged cache: token (b, t) writes pool row ``slots[b, t]``
+    (``ops/kv_pages.py`` ``page_slots``) of kp / vp ``[ng, R + 1, hs]`` through the per-row entries, with the pools'
+    (0, head, row) strides and the capacity ``R``: a token whose slot is the sink row ``R`` (or any row outside
+    ``[0, R)``) writes nothing.  Returns (q, kp, vp) or (q, kp, vp, k_scale, v_scale)."""
+    if not qkv_rope_cache_slots_supported(qkv, cos, sin, kp, vp, slots, n_query_groups, head_size, rope_n, k_scale,
+                                          v_scale):
+        raise ValueError("qkv_rope_cache_slots_fwd: operands the slot write does not take "
+                         "(see qkv_rope_cache_slots_supported)")
+    scales = () if k_scale is None else (k_scale, v_scale)
+    return _qkv_rope_cache_launch(_c(qkv), _c(cos), _c(sin), n_head, n_query_groups, head_size, rope_n,
+                                  (kp, vp, *scales), _c(slots), "_rows", kp.shape[1] - 1, pooled=True)
 
 
 def qkv_rope_rows_fwd(qkv, cos, sin, n_head: int, n_query_groups: int, head_size: int, rope_n: int):
