@@ -119,7 +119,8 @@ def run(mode: str, args) -> dict:
             if sampling:  # every timed generation draws the same tokens
                 torch.manual_seed(args.seed)
             return generate(model, prompt, args.new_tokens, forward=fwd, temperature=args.temperature,
-                            top_k=args.top_k, top_p=args.top_p, prompt_lengths=lengths)
+                            top_k=args.top_k, top_p=args.top_p, prompt_lengths=lengths,
+                            prefill_chunk=args.prefill_chunk)
 
     t0 = time.perf_counter()
     out = once()
@@ -142,7 +143,7 @@ def run(mode: str, args) -> dict:
         "mode": mode, "value": round(ms, 2), "unit": "ms", "higher_is_better": False,
         "ms_per_token": round(ms / args.new_tokens, 3), "first_call_s": round(first, 2),
         "prompt_len": args.prompt_len, "new_tokens": args.new_tokens, "batch_size": args.batch_size,
-        "prompt_lengths": args.prompt_lengths,
+        "prompt_lengths": args.prompt_lengths, "prefill_chunk": None if mode.startswith("hf_") else args.prefill_chunk,
         "kv_cache_dtype": "model" if mode.startswith("hf_") else args.kv_cache_dtype,
         "dtype": "mxfp4 weights, bf16 activations" if mode.endswith("mxfp4") else "bf16",
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
@@ -195,9 +196,14 @@ def main(argv=None):
                         "instead of the static one")
     p.add_argument("--kv-num-pages", type=int, default=None,
                    help="pages per pool of a paged cache (default: what the static cache would hold)")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="LitGPT modes: run the prompt in slices of at most this many columns at 2-D positions "
+                        "(generate(prefill_chunk=...))")
     args = p.parse_args(argv)
     if args.kv_num_pages is not None and args.kv_page_size is None:
         p.error("--kv-num-pages needs --kv-page-size")
+    if args.prefill_chunk is not None and args.prefill_chunk < 1:
+        p.error("--prefill-chunk must be >= 1")
     if args.kv_page_size is not None and any(m.startswith("hf_") for m in args.modes.split(",")):
         p.error("--kv-page-size is for the LitGPT modes")
     if args.prompt_lengths is not None:

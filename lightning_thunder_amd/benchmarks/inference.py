@@ -68,6 +68,7 @@ def _forward_for(mode, model):
 
 
 def run(mode: str, args) -> dict:
+    from ..models.litgpt import _chunked_prefill
     from ..ops.sampling import argmax_last
 
     device = torch.device("cuda", 0)
@@ -99,8 +100,11 @@ def run(mode: str, args) -> dict:
         if pages is not None:
             held = list(host_lengths)
             pages.reserve(held)
-        logits = fwd(prompt, prefill_pos)
-        tok = argmax_last(logits[rows, last] if ragged else logits[:, -1], keepdim=True)
+        if args.prefill_chunk is not None:  # slices of the prompt at 2-D positions, as generate(prefill_chunk=...) runs them
+            tok = argmax_last(_chunked_prefill(fwd, prompt, args.prefill_chunk, lengths if ragged else None), keepdim=True)
+        else:
+            logits = fwd(prompt, prefill_pos)
+            tok = argmax_last(logits[rows, last] if ragged else logits[:, -1], keepdim=True)
         torch.cuda.synchronize()
         ttft = time.perf_counter() - t0
         if ragged:
@@ -146,7 +150,7 @@ def run(mode: str, args) -> dict:
         "latency_ms_per_request": round(1e3 * statistics.mean(totals), 2),
         "first_call_s": round(first, 2),
         "batch_size": B, "input_length": args.input_length, "output_length": n_out,
-        "prompt_lengths": args.prompt_lengths,
+        "prompt_lengths": args.prompt_lengths, "prefill_chunk": args.prefill_chunk,
         "dtype": "bf16", "kv_cache_dtype": args.kv_cache_dtype,
         "kv_cache_gib": round(sum(c.numel() * c.element_size() for b in model.transformer.h
                                   for c in b.attn.kv_cache.buffers()) / 2 ** 30, 3),  # scale buffers included
@@ -179,9 +183,13 @@ def main(argv=None):
                         "static one")
     p.add_argument("--kv-num-pages", type=int, default=None,
                    help="pages per pool of a paged cache (default: what the static cache would hold)")
+    p.add_argument("--prefill-chunk", type=int, default=None,
+                   help="run the prompt in slices of at most this many columns at 2-D positions (chunked prefill)")
     args = p.parse_args(argv)
     if args.kv_num_pages is not None and args.kv_page_size is None:
         p.error("--kv-num-pages needs --kv-page-size")
+    if args.prefill_chunk is not None and args.prefill_chunk < 1:
+        p.error("--prefill-chunk must be >= 1")
     if args.output_length < 1:
         p.error("--output-length must be >= 1")
     if args.prompt_lengths is not None:

@@ -1443,6 +1443,114 @@ def _fuse_kv_paged_reads(trace):
     return rw.finish(f"hipex: {rw.replaced} decode attention(s) read their paged KV cache through the block table")
 
 
+def _kv_prefill_fusion_off() -> bool:
+    """LTA_KV_PREFILL_FUSION=0 keeps a prefill against the KV cache (more than 16 query rows at 2-D positions) as the
+    masked flash attention over the gathered / dequantised cache that the model spells (A/B against the prefill
+    kernel).  The switches of the cache kinds hold here too: LTA_KV_POS_FUSION=0, LTA_KV_PAGED_FUSION=0 and
+    LTA_KV8_FUSION=0 leave the prefill of their kind alone."""
+    return os.environ.get("LTA_KV_PREFILL_FUSION", "1") == "0"
+
+
+def _fuse_kv_prefill_reads(trace):
+    """``hip_flash_attn_fwd_ex(q, k, v, mask, False, scale, 0.0, ...)`` whose LSE nobody reads, at head dim 64 / 128,
+    with ``mask = kv_position_mask(pos, S)`` (``S`` the keys' length) or ``kv_paged_mask(pos, table, page, num_pages)``
+    and ``pos`` int64 ``[B, T]`` -> ``hip_prefill_attn_pos(q, k, v, pos, scale)`` / ``hip_prefill_attn_paged(q, kp, vp,
+    pos, table, page, num_pages, scale)``: the kernel takes every row's key count from its position (and every key's
+    pool row from the block table), so a prefill builds no ``[B, 1, T, S]`` mask image, sweeps no key tile beyond its
+    rows' positions, and neither gathers nor dequantises the cache.
+
+    k / v are the raw cache, ``to(view(cache, float8_e4m3fn), q.dtype)`` of a uint8 cache (``_kv8`` forms) or
+    ``kv8_dequantise_rows(cache, scales, q.dtype)`` (``_kv8s`` forms), both of one kind; under the paged mask every
+    cache operand is a ``kv_paged_gather`` read once, all at the mask's table and page size (``PagedKVCache.forward``
+    dequantises the gather of a pool).  Nothing may write a cache or pool in place between the first of those links
+    and the attention.  The links are dropped when nothing else reads them, the mask (one serves the layers of a
+    step) with its last reader.  Anything else stays as it is: a read LSE, ``causal``, dropout, a float mask, another
+    head dim, k and v of different kinds, the 1-D ``input_pos`` route (``mask_cache.index_select``)."""
+    if _kv_prefill_fusion_off():
+        return trace
+    rw = Rewrite(trace, ex)
+    ops = {"16bit": (hip_prefill_attn_pos, hip_prefill_attn_paged),
+           "kv8": (hip_prefill_attn_kv8_pos, hip_prefill_attn_kv8_paged),
+           "kv8s": (hip_prefill_attn_kv8s_pos, hip_prefill_attn_kv8s_paged)}
+    masks = set()
+    for i, b in enumerate(rw.bsyms):
+        if b.sym is not hip_attn_fwd_ex or rw.touched(i):
+            continue
+        p = operands(b)
+        q, k, v, mask = p["q"], p["k"], p["v"], p["mask"]
+        if not isinstance(b.output, (tuple, list)) or len(b.output) != 2 or rw.uses(b.output[1]):
+            continue
+        if p["causal"] or isinstance(p["dropout_p"], Proxy) or p["dropout_p"] or q.shape[-1] not in (64, 128):
+            continue
+        if not all(isinstance(t, TensorProxy) for t in (k, v, mask)) or mask.dtype != torch.bool:
+            continue
+        m = rw.producer(mask)
+        if m is None or rw.touched(m):
+            continue
+        mb = rw.bsyms[m]
+        paged = mb.sym.id in _KV_PAGED_MASK_IDS
+        if paged:
+            pm = operands(mb, ("pos", "table", "page_size", "num_pages"))
+            pos, table = pm["pos"], pm["table"]
+            if _kv_paged_fusion_off() or not isinstance(table, TensorProxy):
+                continue
+            if any(isinstance(pm[n], Proxy) for n in ("page_size", "num_pages")):
+                continue
+        elif mb.sym.id in _KV_POSITION_MASK_IDS:
+            pm = operands(mb, ("input_pos", "S"))
+            pos = pm["input_pos"]
+            if _kv_pos_fusion_off() or isinstance(pm["S"], Proxy) or k.ndim != 4 or k.shape[2] != int(pm["S"]):
+                continue
+        else:
+            continue
+        if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or pos.ndim != 2:
+            continue
+        if tuple(pos.shape) != (q.shape[0], q.shape[2]):
+            continue
+        # the cache kind: k and v through the same dequantise, or both as they are stored
+        kinds = (("kv8s", _kv8_rows_dequantised), ("kv8", _e4m3_dequantised))
+        found = [(kind, resolve(rw, k, q.dtype), resolve(rw, v, q.dtype)) for kind, resolve in kinds]
+        hit = [f for f in found if f[1] is not None and f[2] is not None]
+        if hit:
+            kind, rk, rv = hit[0]
+            if _kv8_fusion_off():
+                continue
+        elif any(f[1] is not None or f[2] is not None for f in found) or k.dtype != q.dtype or v.dtype != q.dtype:
+            continue
+        else:
+            kind, rk, rv = "16bit", ((k,), i, ()), ((v,), i, ())
+        caches = [c for pair in zip(rk[0], rv[0]) for c in pair]  # the operators' order: k, v, then their scales
+        chains = [list(rk[2]), list(rv[2])]  # per operand: the links to drop, outermost first
+        first = min(rk[1], rv[1])
+        if paged:
+            gathers = [_paged_gather(rw, c) for c in caches]
+            if any(g is None or g[1].name != table.name or g[2] != pm["page_size"] for g in gathers):
+                continue
+            for n, g in enumerate(gathers):
+                chains[n % 2].append(g[3])
+            caches = [g[0] for g in gathers]
+            first = min(first, *(g[3] for g in gathers))
+        # the kernel reads the caches where the attention stands: nothing may write them after the first link
+        if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
+               for c in caches for j in rw.consumers(c)):
+            continue
+        rest = (pos, table, pm["page_size"], pm["num_pages"]) if paged else (pos,)
+        rw.replace(i, ops[kind][paged].bind(q, *caches, *rest, p["scale"], output=b.output[0]))
+        for chain in chains:
+            for j in chain:
+                # a link goes when its only reader was the attention or a link just dropped (a scaled paged cache has
+                # two gathers under one dequantise)
+                link = rw.bsyms[j].output
+                if rw.uses(link) != 1 or not all(c == i or rw.dropped(c) for c in rw.consumers(link)):
+                    break
+                rw.drop(j)
+        masks.add(m)
+    for m in masks:  # one mask serves the layers of a step
+        if all(rw.touched(j) and not rw.dropped(j) for j in rw.consumers(rw.bsyms[m].output)):
+            rw.drop(m)
+    return rw.finish(f"hipex: {rw.replaced} prefill attention(s) read their KV cache by positions")
+
+
 def _fuse_rms_bwd_residual(trace):
     """``(dx, dw) = hip_rms_norm_bwd(g, x, w, rstd); z = dx + r`` (dx used nowhere else) ->
     ``(z, dw) = hip_rms_norm_bwd(g, x, w, rstd, r)``: the residual stream's gradient is added in the
@@ -1833,6 +1941,7 @@ _PASSES = (
             message="hipex: MXFP4 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
                     "{norm} norm prologue(s), {group} group(s))"),
     _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv_position_reads, _fuse_kv8_reads, _fuse_kv_paged_reads,
+    _fuse_kv_prefill_reads,
     partial(_fuse_decode, kind=_BF16_DECODE, folds=("group",), message="hipex: {group} grouped decode projection launch(es)"),
     _fuse_qkv_rope_gemm, _fuse_fp8_qkv_rope_gemm, _fuse_attn_bwd_rope,
 )
@@ -2346,6 +2455,93 @@ hip_decode_attn_kv8s_paged = ex.register_operator(
     "hip_decode_attn_kv8s_paged",
     meta=lambda q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale: TensorProxy(like=q),
     fn=_decode_attn_kv8s_paged_impl)
+
+
+# The prefill forms (csrc/prefill_attention.hip): the position and paged forms above for any number of query rows, in
+# place of the masked flash attention over the gathered / dequantised cache.  Each runs its kernel where
+# ``*_supported`` takes the operands, else the program as the model spells it.
+def _prefill_attn_pos_impl(q, k, v, pos, scale):
+    from ..ops.attention import attn_fwd, prefill_attn_pos, prefill_attn_pos_supported
+    from ..ops.kv_rows import position_mask
+
+    if prefill_attn_pos_supported(q, k, v, pos):
+        return prefill_attn_pos(q, k, v, pos, scale)
+    return attn_fwd(q, k, v, False, scale, mask=position_mask(pos, k.shape[2]))[0]
+
+
+def _prefill_attn_kv8_pos_impl(q, k8, v8, pos, scale):
+    from ..ops.attention import prefill_attn_kv8_pos, prefill_attn_kv8_pos_supported
+    from ..ops.kv8 import e4m3_values
+
+    if prefill_attn_kv8_pos_supported(q, k8, v8, pos):
+        return prefill_attn_kv8_pos(q, k8, v8, pos, scale)
+    return _prefill_attn_pos_impl(q, e4m3_values(k8, q.dtype), e4m3_values(v8, q.dtype), pos, scale)
+
+
+def _prefill_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale):
+    from ..ops.attention import prefill_attn_kv8s_pos, prefill_attn_kv8s_pos_supported
+    from ..ops.kv8 import dequantise_rows
+
+    if prefill_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
+        return prefill_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale)
+    return _prefill_attn_pos_impl(q, dequantise_rows(k8, k_scale, q.dtype), dequantise_rows(v8, v_scale, q.dtype), pos,
+                                  scale)
+
+
+def _prefill_attn_unpaged(q, caches, mask, scale):
+    """The masked flash attention over gathered ``caches`` in operator order (k, v, then scale caches)."""
+    from ..ops.attention import attn_fwd
+    from ..ops.kv8 import dequantise_rows, e4m3_values
+
+    if len(caches) == 4:
+        k, v = dequantise_rows(caches[0], caches[2], q.dtype), dequantise_rows(caches[1], caches[3], q.dtype)
+    elif caches[0].dtype == torch.uint8:
+        k, v = e4m3_values(caches[0], q.dtype), e4m3_values(caches[1], q.dtype)
+    else:
+        k, v = caches
+    return attn_fwd(q, k, v, False, scale, mask=mask)[0]
+
+
+def _prefill_attn_paged_impl(q, k, v, pos, table, page_size, num_pages, scale):
+    from ..ops.attention import prefill_attn_paged, prefill_attn_paged_supported
+
+    if prefill_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
+        return prefill_attn_paged(q, k, v, pos, table, page_size, num_pages, scale)
+    return _prefill_attn_unpaged(q, *_paged_selector((k, v), pos, table, page_size, num_pages), scale)
+
+
+def _prefill_attn_kv8_paged_impl(q, k8, v8, pos, table, page_size, num_pages, scale):
+    from ..ops.attention import prefill_attn_kv8_paged, prefill_attn_kv8_paged_supported
+
+    if prefill_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
+        return prefill_attn_kv8_paged(q, k8, v8, pos, table, page_size, num_pages, scale)
+    return _prefill_attn_unpaged(q, *_paged_selector((k8, v8), pos, table, page_size, num_pages), scale)
+
+
+def _prefill_attn_kv8s_paged_impl(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale):
+    from ..ops.attention import prefill_attn_kv8s_paged, prefill_attn_kv8s_paged_supported
+
+    if prefill_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
+        return prefill_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale)
+    caches, mask = _paged_selector((k8, v8, k_scale, v_scale), pos, table, page_size, num_pages)
+    return _prefill_attn_unpaged(q, caches, mask, scale)
+
+
+hip_prefill_attn_pos = ex.register_operator("hip_prefill_attn_pos", meta=_decode_attn_pos_meta,
+                                            fn=_prefill_attn_pos_impl)
+hip_prefill_attn_kv8_pos = ex.register_operator("hip_prefill_attn_kv8_pos", meta=_decode_attn_pos_meta,
+                                                fn=_prefill_attn_kv8_pos_impl)
+hip_prefill_attn_kv8s_pos = ex.register_operator(
+    "hip_prefill_attn_kv8s_pos", meta=lambda q, k8, v8, k_scale, v_scale, pos, scale: TensorProxy(like=q),
+    fn=_prefill_attn_kv8s_pos_impl)
+hip_prefill_attn_paged = ex.register_operator("hip_prefill_attn_paged", meta=_decode_attn_paged_meta,
+                                              fn=_prefill_attn_paged_impl)
+hip_prefill_attn_kv8_paged = ex.register_operator("hip_prefill_attn_kv8_paged", meta=_decode_attn_paged_meta,
+                                                  fn=_prefill_attn_kv8_paged_impl)
+hip_prefill_attn_kv8s_paged = ex.register_operator(
+    "hip_prefill_attn_kv8s_paged",
+    meta=lambda q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale: TensorProxy(like=q),
+    fn=_prefill_attn_kv8s_paged_impl)
 
 
 def _broadcastable(shape, target) -> bool:

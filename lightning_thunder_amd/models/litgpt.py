@@ -665,7 +665,8 @@ def flops_per_token(config: Config, seq_len: int, training: bool = True) -> floa
 @torch.no_grad()
 def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, temperature: float = 0.0,
              top_k: Optional[int] = None, top_p: Optional[float] = None, eos_id: Optional[int] = None,
-             prompt_lengths: Optional[torch.Tensor] = None, pad_id: int = 0) -> torch.Tensor:
+             prompt_lengths: Optional[torch.Tensor] = None, pad_id: int = 0,
+             prefill_chunk: Optional[int] = None) -> torch.Tensor:
     """Autoregressive generation with the static KV cache (LitGPT ``generate``).
 
     ``forward`` is the callable used for every step (default: ``model``; pass ``thunder.jit(model)``).
@@ -680,21 +681,33 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
 
     ``prompt_lengths`` (int64 ``[B]``, ``1 <= len_b <= T``) makes the batch ragged: ``prompt`` is right-padded
     and row b holds ``len_b`` real tokens; see :func:`_generate_ragged`.  ``pad_id`` is only used there.
+
+    ``prefill_chunk`` (a positive int, else ``ValueError``) runs the prompt in slices of at most that many columns,
+    each one ``forward(prompt[:, c0:c1], pos2d)`` at the int64 ``[B, c1 - c0]`` positions ``arange(c0, c1)``, on every
+    route (plain, ragged, paged): a prompt longer than one forward's activations allow still prefills, and every
+    chunk attends the cache by positions (``hip_prefill_attn_*`` under the HIP executor).  A value ``>= T`` is one
+    chunk: the whole prompt by positions.  ``None`` prefills as before; the decode loop is the same either way.
     """
     from ..ops.sampling import argmax_last, sample_last
 
+    if prefill_chunk is not None and (isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, int)
+                                      or prefill_chunk < 1):
+        raise ValueError(f"generate: prefill_chunk must be a positive int or None, got {prefill_chunk!r}")
     forward = forward or model
     if prompt_lengths is None and getattr(model, "kv_pages", None) is not None:  # a paged cache: always the ragged route
         prompt_lengths = torch.full((prompt.shape[0],), prompt.shape[1], device=prompt.device, dtype=torch.int64)
     if prompt_lengths is not None:
         return _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k, top_p, eos_id,
-                                prompt_lengths, pad_id)
+                                prompt_lengths, pad_id, prefill_chunk)
     B, T = prompt.shape
     if model.transformer.h[0].attn.kv_cache is None:
         raise RuntimeError("call model.set_kv_cache(batch_size, max_seq_length) first")
     device = prompt.device
-    input_pos = torch.arange(T, device=device)
-    logits = forward(prompt, input_pos)
+    if prefill_chunk is None:
+        input_pos = torch.arange(T, device=device)
+        logits = forward(prompt, input_pos)
+    else:
+        logits = _chunked_prefill(forward, prompt, prefill_chunk)[:, None]
     out = [prompt]
     pos = torch.tensor([T], device=device, dtype=torch.int64)
     for i in range(max_new_tokens):
@@ -712,8 +725,31 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
     return torch.cat(out, dim=1)
 
 
+def _chunked_prefill(forward, prompt, chunk: int, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The prompt ``[B, T]`` through ``forward`` in slices of at most ``chunk`` columns at the 2-D positions
+    ``arange(c0, c1)``.  Returns the logits ``[B, V]`` every sequence's first new token is drawn from: those of column
+    ``lengths[b] - 1`` (``T - 1`` without ``lengths``), picked out of the chunk that holds it; no other logits are kept."""
+    B, T = prompt.shape
+    device = prompt.device
+    rows = torch.arange(B, device=device)
+    last = None
+    for c0 in range(0, T, chunk):
+        c1 = min(T, c0 + chunk)
+        pos2d = torch.arange(c0, c1, device=device, dtype=torch.int64).expand(B, c1 - c0).contiguous()
+        logits = forward(prompt[:, c0:c1], pos2d)
+        if lengths is None:
+            if c1 == T:
+                last = logits[:, -1]
+            continue
+        col = lengths - 1 - c0  # the column of this chunk that holds a sequence's last prompt token, if any does
+        here = (col >= 0) & (col < c1 - c0)
+        picked = logits[rows, col.clamp(0, c1 - c0 - 1)]
+        last = picked if last is None else torch.where(here[:, None], picked, last)
+    return last
+
+
 def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k, top_p, eos_id, prompt_lengths,
-                     pad_id) -> torch.Tensor:
+                     pad_id, prefill_chunk=None) -> torch.Tensor:
     """``generate`` for a right-padded ``[B, Tmax]`` prompt whose row b holds ``prompt_lengths[b]`` tokens.
 
     Prefill runs the padded prompt at the shared ``arange(Tmax)``: a pad token writes K/V rows at positions
@@ -726,7 +762,10 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
 
     On a paged cache (``set_kv_cache(page_size=...)``) the prefill runs at ``arange(Tmax)`` expanded to ``[B, Tmax]``
     after ``model.kv_pages.reserve(prompt_lengths)``, and before every decode step the sequences that are not
-    finished get room for one more token, from host-side counters; a finished sequence receives no further page.  Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
+    finished get room for one more token, from host-side counters; a finished sequence receives no further page.
+
+    With ``prefill_chunk`` the prefill is ``_chunked_prefill`` on either cache: slices of the padded prompt at 2-D
+    positions, after the prompts' pages are reserved; a pad token's K/V row is overwritten as above.  Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
     from column ``len_b`` on, then ``pad_id``."""
     from ..ops.sampling import argmax_last, sample_last
 
@@ -752,15 +791,20 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
     if max_new_tokens <= 0:
         return out
     if pages is None:
-        logits = forward(prompt, torch.arange(T, device=device))
+        if prefill_chunk is None:
+            logits = forward(prompt, torch.arange(T, device=device))
     else:
         # pages for the prompts; a pad token beyond its sequence's last page has no slot and falls to the sink row
         held = lengths.tolist()  # host-side counters from here on
         live = [True] * B
         pages.reset()  # a generation starts from an empty table, as it overwrites a static cache
         pages.reserve(held)
-        logits = forward(prompt, torch.arange(T, device=device).expand(B, T).contiguous())
-    last = logits[torch.arange(B, device=device), lengths - 1]
+        if prefill_chunk is None:
+            logits = forward(prompt, torch.arange(T, device=device).expand(B, T).contiguous())
+    if prefill_chunk is None:
+        last = logits[torch.arange(B, device=device), lengths - 1]
+    else:
+        last = _chunked_prefill(forward, prompt, prefill_chunk, lengths)
     pos = lengths.clone().view(B, 1)  # where the next token of every sequence goes; advanced in place
     done = torch.zeros(B, 1, device=device, dtype=torch.bool)
     for i in range(max_new_tokens):

@@ -456,11 +456,12 @@ def _refusal(fn: str, **operands) -> ValueError:
         f"{name} {None if t is None else (t.dtype, tuple(t.shape))}" for name, t in operands.items()))
 
 
-def _cache_operands_ok(q, k, v, cache_dtype) -> bool:
+def _cache_operands_ok(q, k, v, cache_dtype, max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
     """The shape rule of every kernel that checks its operands: 16-bit q [B, Hq, T, D] with D 64 / 128 and at most
-    DECODE_MAX_QUERIES rows, k / v [B, Hkv, S, D] of ``cache_dtype`` with Hkv dividing Hq."""
+    ``max_queries`` rows (the decode kernels' DECODE_MAX_QUERIES; None for the prefill kernel: any number), k / v
+    [B, Hkv, S, D] of ``cache_dtype`` with Hkv dividing Hq."""
     return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
-            and q.shape[2] <= DECODE_MAX_QUERIES and k.dtype == cache_dtype and v.dtype == cache_dtype
+            and (max_queries is None or q.shape[2] <= max_queries) and k.dtype == cache_dtype and v.dtype == cache_dtype
             and k.dim() == 4 and k.shape == v.shape and k.shape[-1] == q.shape[-1] and k.shape[0] == q.shape[0]
             and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0)
 
@@ -516,11 +517,11 @@ def decode_attn_kv8s(q, k8, v8, k_scale, v_scale, mask=None, causal: bool = Fals
 # ------------------------------------------------------------------------------------------------
 # Position mode of the decode kernels (ragged batches): every row's key count from pos[b, t], no mask
 # ------------------------------------------------------------------------------------------------
-def _pos_ok(q, k, pos) -> bool:
-    """int64 positions [B, T] (any strides) on q's device, at most DECODE_MAX_QUERIES query rows."""
+def _pos_ok(q, k, pos, max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
+    """int64 positions [B, T] (any strides) on q's device, at most ``max_queries`` query rows (None: any number)."""
     return (pos is not None and pos.dtype == torch.int64 and pos.dim() == 2 and q.dim() == 4 and k.dim() == 4
             and tuple(pos.shape) == (q.shape[0], q.shape[2]) and pos.device == q.device
-            and 0 < q.shape[2] <= DECODE_MAX_QUERIES)
+            and 0 < q.shape[2] and (max_queries is None or q.shape[2] <= max_queries))
 
 
 def decode_attn_pos_supported(q, k, v, pos) -> bool:
@@ -567,9 +568,10 @@ def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None =
 # ------------------------------------------------------------------------------------------------
 # Paged mode of the decode kernels (ops/kv_pages.py): the position mode with every key's row taken from a block table
 # ------------------------------------------------------------------------------------------------
-def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=()) -> bool:
-    """16-bit q [B, Hq, T, D] with D 64 / 128 and at most DECODE_MAX_QUERIES rows; pools k / v [Hkv, rows, D] of
-    ``cache_dtype`` read in place (head dim contiguous, 16-byte aligned rows and heads) with Hkv dividing Hq and
+def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=(),
+              max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
+    """16-bit q [B, Hq, T, D] with D 64 / 128 and at most ``max_queries`` rows (None: any number); pools k / v
+    [Hkv, rows, D] of ``cache_dtype`` read in place (head dim contiguous, 16-byte aligned rows and heads) with Hkv dividing Hq and
     ``rows >= num_pages * page_size``; scale pools uint8 [Hkv, rows, 1]; int64 ``pos`` [B, T] and ``table``
     [B, max_pages >= 1] on q's device; ``page_size`` a power of two >= 16 and ``num_pages`` >= 1, both ints."""
     if not all(isinstance(n, int) and not isinstance(n, bool) for n in (page_size, num_pages)):
@@ -577,7 +579,7 @@ def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=())
     if page_size < 16 or page_size & (page_size - 1) or num_pages < 1 or num_pages * page_size >= 2 ** 31:
         return False
     if not (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
-            and 0 < q.shape[2] <= DECODE_MAX_QUERIES):
+            and 0 < q.shape[2] and (max_queries is None or q.shape[2] <= max_queries)):
         return False
     unit = 16 // k.element_size()  # elements per 16 bytes
     for c in (k, v):
@@ -636,3 +638,126 @@ def decode_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size: i
                        table=table)
     return _decode_launch("lta_decode_attn_kv8s_paged", _rows_in_place(q), k8, v8, scale, pos=pos,
                           scales=(k_scale, v_scale), pages=(table, page_size, num_pages))
+
+
+# ------------------------------------------------------------------------------------------------
+# K3p prefill attention by positions (csrc/prefill_attention.hip): the flash forward for any number of query rows
+# that sit at positions of a KV cache; the position and paged modes of the decode kernels above, past 16 rows
+# ------------------------------------------------------------------------------------------------
+# the prefill entries: pointers q, k, v, <scale caches>, pos, o, then the sizes, the stride record, O's strides and the
+# softmax scale; the paged entries go on with the block table, log2 of the page size and the page count
+for _entry, _scale_ptrs in (("lta_prefill_attn", 0), ("lta_prefill_attn_kv8", 0), ("lta_prefill_attn_kv8s", 2)):
+    _head = [c_int, *[c_void_p] * (5 + _scale_ptrs), *[c_int] * 6, c_void_p, c_void_p, c_float]
+    register_signature(_entry + "_pos", [*_head, c_void_p])
+    register_signature(_entry + "_paged", [*_head, c_void_p, c_int, c_int, c_void_p])
+
+
+def _prefill_launch(entry: str, q, k, v, pos, scale: float | None, scales=(), pages=None):
+    """One launch of the prefill entry ``entry`` (operands as ``_decode_launch`` takes them in its position mode).  O
+    is stored ``[B, T, Hq, D]`` and returned as its ``[B, Hq, T, D]`` view, as ``attn_fwd`` does.  The grid comes from
+    the shapes alone: positions and table stay on the device, so the launch is capturable."""
+    lib = require()
+    B, Hq, T, D = q.shape
+    if pages is not None:
+        table, page_size, num_pages = pages
+        Hkv, S = k.shape[0], table.shape[1] * page_size
+        cache_st = lambda c: (0, *c.stride()[:2])
+        tail = (*table.stride(), ptr(table), page_size.bit_length() - 1, num_pages)
+    else:
+        Hkv, S = k.shape[1], k.shape[2]
+        cache_st = lambda c: c.stride()[:3]
+        tail = ()
+    sc = scale if scale is not None else 1.0 / math.sqrt(D)
+    o = torch.empty((B, T, Hq, D), device=q.device, dtype=q.dtype).transpose(1, 2)
+    st = (*q.stride()[:3], *cache_st(k), *cache_st(v), *pos.stride(), *(s for c in scales for s in cache_st(c)), *tail[:2])
+    st = (ctypes.c_int64 * len(st))(*st)
+    rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *map(ptr, scales), ptr(pos), ptr(o), B, Hq, Hkv, T, S, D,
+                             ctypes.cast(st, c_void_p), ctypes.cast(_strides3(o), c_void_p), float(sc), *tail[2:],
+                             stream_ptr(q.device))
+    check(rc, entry)
+    return o
+
+
+def prefill_attn_pos_supported(q, k, v, pos) -> bool:
+    """What the 16-bit prefill kernel takes: bf16 / fp16 q, k, v of one dtype and head dim 64 / 128, GQA head counts,
+    int64 ``pos`` [B, T] with any T >= 1, a cache of at least one key."""
+    return _pos_ok(q, k, pos, None) and _cache_operands_ok(q, k, v, q.dtype, None) and k.shape[2] > 0
+
+
+def prefill_attn_kv8_pos_supported(q, k8, v8, pos) -> bool:
+    return _pos_ok(q, k8, pos, None) and _cache_operands_ok(q, k8, v8, torch.uint8, None) and k8.shape[2] > 0
+
+
+def prefill_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos) -> bool:
+    return prefill_attn_kv8_pos_supported(q, k8, v8, pos) and scale_caches_of((k_scale, v_scale), (k8, v8))
+
+
+def prefill_attn_pos(q, k, v, pos, scale: float | None = None):
+    """Attention of query rows at positions of a KV cache: q [B, Hq, T, D] (any T >= 1), k / v [B, Hkv, S, D], ``pos``
+    int64 [B, T] (need not be monotone).  Row (b, hq, t) attends keys ``0 .. n-1`` with ``n = clamp(pos[b, t] + 1, 0,
+    S)``: what ``attn_fwd(q, k, v, causal=False, mask=position_mask(pos, S))[0]`` computes, bit for bit, without the
+    mask image and over the key tiles some row can see only.  ``n = 0`` gives a row of zeros, as there."""
+    if not prefill_attn_pos_supported(q, k, v, pos):
+        raise _refusal("prefill_attn_pos", q=q, k=k, v=v, pos=pos)
+    q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
+    return _prefill_launch("lta_prefill_attn_pos", q, k, v, pos, scale)
+
+
+def prefill_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None):
+    """``prefill_attn_pos`` over an unscaled e4m3 cache (uint8 bytes of ``float8_e4m3fn``): equals it over
+    ``e4m3_values(k8, q.dtype)`` / ``e4m3_values(v8, q.dtype)`` bit for bit."""
+    if not prefill_attn_kv8_pos_supported(q, k8, v8, pos):
+        raise _refusal("prefill_attn_kv8_pos", q=q, k=k8, v=v8, pos=pos)
+    return _prefill_launch("lta_prefill_attn_kv8_pos", *_e4m3_in_place(q, k8, v8), pos, scale)
+
+
+def prefill_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None):
+    """``prefill_attn_pos`` over the scaled e4m3 cache of ``ops/kv8.py``: equals it over ``dequantise_rows`` of the
+    caches bit for bit; the scales are read in place."""
+    if not prefill_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
+        raise _refusal("prefill_attn_kv8s_pos", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos)
+    return _prefill_launch("lta_prefill_attn_kv8s_pos", *_e4m3_in_place(q, k8, v8), pos, scale,
+                           scales=(k_scale, v_scale))
+
+
+def prefill_attn_paged_supported(q, k, v, pos, table, page_size, num_pages) -> bool:
+    """What the 16-bit paged prefill kernel takes: see ``_paged_ok``, with pools of q's dtype and any T >= 1."""
+    return _paged_ok(q, k, v, pos, table, page_size, num_pages, q.dtype, max_queries=None)
+
+
+def prefill_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages) -> bool:
+    return _paged_ok(q, k8, v8, pos, table, page_size, num_pages, torch.uint8, max_queries=None)
+
+
+def prefill_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages) -> bool:
+    return _paged_ok(q, k8, v8, pos, table, page_size, num_pages, torch.uint8, (k_scale, v_scale), max_queries=None)
+
+
+def prefill_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+    """``prefill_attn_pos`` over a paged cache: k / v pools ``[Hkv, R + 1, D]``, ``table`` int64 ``[B, max_pages]``.
+    Row (b, hq, t) attends the keys ``j <= pos[b, t]`` (clamped to the capacity ``S = max_pages * page_size``) whose
+    table entry lies in ``[0, num_pages)``, each read at pool row ``table[b, j // page_size] * page_size + j %
+    page_size``: what ``attn_fwd`` computes over ``gather_pages`` under ``paged_mask``, bit for bit.  A row without a
+    live key is zeros."""
+    if not prefill_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
+        raise _refusal("prefill_attn_paged", q=q, k=k, v=v, pos=pos, table=table)
+    return _prefill_launch("lta_prefill_attn_paged", _rows_in_place(q), k, v, pos, scale,
+                           pages=(table, page_size, num_pages))
+
+
+def prefill_attn_kv8_paged(q, k8, v8, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+    """``prefill_attn_paged`` over unscaled e4m3 pools (uint8)."""
+    if not prefill_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
+        raise _refusal("prefill_attn_kv8_paged", q=q, k=k8, v=v8, pos=pos, table=table)
+    return _prefill_launch("lta_prefill_attn_kv8_paged", _rows_in_place(q), k8, v8, pos, scale,
+                           pages=(table, page_size, num_pages))
+
+
+def prefill_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size: int, num_pages: int,
+                            scale: float | None = None):
+    """``prefill_attn_paged`` over the scaled e4m3 pools: bytes ``[Hkv, R + 1, D]`` and scale bytes ``[Hkv, R + 1, 1]``."""
+    if not prefill_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
+        raise _refusal("prefill_attn_kv8s_paged", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos,
+                       table=table)
+    return _prefill_launch("lta_prefill_attn_kv8s_paged", _rows_in_place(q), k8, v8, pos, scale,
+                           scales=(k_scale, v_scale), pages=(table, page_size, num_pages))
