@@ -1,5 +1,5 @@
 """Shared assertions of the kernel-against-fp64 batteries (test_decode_kernels.py, test_train_row_kernels.py,
-test_attention_kernels.py, test_gemm_kernels.py), the mirror of the attention kernels' dropout hash, and the
+test_attention_kernels.py, test_gemm_kernels.py, test_hipfuse_kernels.py), the mirror of the attention kernels' dropout hash, and the
 guard / poison buffers that show a kernel writing outside its result or reading outside its operands.
 
 Tolerance of every rounded output, per element:  ulp(T) * |ref64| + 8 * e32 + floor.
@@ -135,6 +135,39 @@ def nan_padded(t, pad_rows=8, pad_cols=8):
     view = buf[..., :R, :C]
     view.copy_(t)
     return view
+
+
+def offset_by_one(t):
+    """A contiguous copy of ``t`` that starts one element into its buffer: on the GPU its address is no
+    multiple of 16 bytes."""
+    buf = torch.full((t.numel() + 1,), float("nan"), dtype=t.dtype, device=t.device)
+    view = buf[1:].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and (t.device.type == "cpu" or view.data_ptr() % 16 != 0)
+    return view
+
+
+def odd_pitch(t):
+    """A view equal to ``t`` (>= 2-D): the leading columns of a NaN-filled base one element wider, so the
+    stride of the second-to-last dim is the column count plus one."""
+    *lead, R, C = t.shape
+    base = torch.full((*lead, R, C + 1), float("nan"), dtype=t.dtype, device=t.device)
+    view = base[..., :C]
+    view.copy_(t)
+    return view
+
+
+def assert_within_finite(out, ref64, ref32, dtype, group, what="", rel_floor=False, extra=None):
+    """:func:`assert_within` for a reference with NaN or infinite elements: those must sit at the same
+    positions of ``out`` (infinities with their sign), the finite remainder is held to the tolerance."""
+    assert out.shape == ref64.shape, (out.shape, ref64.shape)
+    nan, inf = torch.isnan(ref64), torch.isinf(ref64)
+    assert torch.equal(torch.isnan(out), nan), f"{what}: NaN at other positions than the reference's"
+    assert torch.equal(out[inf].double(), ref64[inf]), f"{what}: infinities differ from the reference's"
+    fin = ~(nan | inf)
+    assert fin.any(), f"{what}: nothing finite is left to compare"
+    assert_within(out[fin], ref64[fin], ref32[fin], dtype, group, what, rel_floor=rel_floor,
+                  extra=None if extra is None else extra[fin])
 
 
 def poison(t):
