@@ -37,10 +37,12 @@ from . import KV_CACHE_FORMATS
 
 
 def _build(model_name: str, max_seq: int, device, n_layer=None, kv_cache_dtype: str = "model", batch_size: int = 1,
-           page_size=None, num_pages=None):
+           page_size=None, num_pages=None, sliding_window=None):
     from ..models.litgpt import GPT, Config, init_weights
 
     kw = {} if n_layer is None else {"n_layer": n_layer}
+    if sliding_window is not None:  # every layer attends its last N keys, whatever the config says
+        kw.update(sliding_window_size=sliding_window, sliding_window_indices=None)
     cfg = Config.from_name(model_name, **kw)
     with torch.device("meta"):
         model = GPT(cfg)
@@ -95,7 +97,7 @@ def run(mode: str, args) -> dict:
             return gm.generate(prompt, **kw)
     else:
         model, cfg = _build(args.model, args.prompt_len + args.new_tokens + 8, device, args.n_layer, args.kv_cache_dtype,
-                            args.batch_size, args.kv_page_size, args.kv_num_pages)
+                            args.batch_size, args.kv_page_size, args.kv_num_pages, args.sliding_window)
         prompt = torch.randint(0, cfg.vocab_size, (args.batch_size, args.prompt_len), device=device)
         lengths = None
         if args.prompt_lengths is not None:
@@ -154,7 +156,9 @@ def run(mode: str, args) -> dict:
         res["kv_cache_gib"] = round(sum(t.numel() * t.element_size() for c in caches for t in c.buffers()) / 2 ** 30, 3)
         pages = model.kv_pages
         res.update(kv_page_size=args.kv_page_size, kv_num_pages=None if pages is None else pages.num_pages,
-                   kv_pages_in_use=None if pages is None else pages.pages_in_use)
+                   kv_pages_in_use=None if pages is None else pages.pages_in_use,
+                   kv_pages_peak=None if pages is None else pages.peak_pages_in_use,  # of the last generation
+                   sliding_window=cfg.sliding_window_size)
     if sampling:
         res.update(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=args.seed)
     first_new = args.prompt_lengths[0] if args.prompt_lengths and not mode.startswith("hf_") else out.shape[1] - args.new_tokens
@@ -199,7 +203,12 @@ def main(argv=None):
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="LitGPT modes: run the prompt in slices of at most this many columns at 2-D positions "
                         "(generate(prefill_chunk=...))")
+    p.add_argument("--sliding-window", type=int, default=None,
+                   help="LitGPT modes: a sliding window of this many keys on every layer (overrides the model's config); "
+                        "with a paged cache generate() hands the pages below the window back to the pool")
     args = p.parse_args(argv)
+    if args.sliding_window is not None and args.sliding_window < 1:
+        p.error("--sliding-window must be >= 1")
     if args.kv_num_pages is not None and args.kv_page_size is None:
         p.error("--kv-num-pages needs --kv-page-size")
     if args.prefill_chunk is not None and args.prefill_chunk < 1:

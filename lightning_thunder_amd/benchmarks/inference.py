@@ -40,6 +40,8 @@ def _build(args, device):
     from ..models.litgpt import GPT, Config, init_weights
 
     kw = {} if args.n_layer is None else {"n_layer": args.n_layer}
+    if args.sliding_window is not None:  # every layer attends its last N keys, whatever the config says
+        kw.update(sliding_window_size=args.sliding_window, sliding_window_indices=None)
     cfg = Config.from_name(args.model, **kw)
     with torch.device("meta"):
         model = GPT(cfg)
@@ -82,6 +84,8 @@ def run(mode: str, args) -> dict:
     pages = model.kv_pages  # a paged cache (--kv-page-size) takes one position per token: the ragged route
     ragged = args.prompt_lengths is not None or pages is not None
     host_lengths = args.prompt_lengths or [args.input_length] * args.batch_size
+    # every layer under one window: a paged cache gives up the pages below it, as generate() does
+    trim = cfg.uniform_window if pages is not None else None
     if pages is not None:
         prefill_pos = prefill_pos.expand(args.batch_size, -1).contiguous()
     if ragged:
@@ -97,11 +101,18 @@ def run(mode: str, args) -> dict:
             pages.reset()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        move_pages = None
         if pages is not None:
             held = list(host_lengths)
-            pages.reserve(held)
+            if trim is None or args.prefill_chunk is None:
+                pages.reserve(held)
+            else:  # pages chunk by chunk, those below the chunk's windows handed back first
+                def move_pages(c0, c1):
+                    pages.trim([max(0, min(c0, n) - trim + 1) for n in held])
+                    pages.reserve([min(c1, n) for n in held])
         if args.prefill_chunk is not None:  # slices of the prompt at 2-D positions, as generate(prefill_chunk=...) runs them
-            tok = argmax_last(_chunked_prefill(fwd, prompt, args.prefill_chunk, lengths if ragged else None), keepdim=True)
+            tok = argmax_last(_chunked_prefill(fwd, prompt, args.prefill_chunk, lengths if ragged else None,
+                                               move_pages), keepdim=True)
         else:
             logits = fwd(prompt, prefill_pos)
             tok = argmax_last(logits[rows, last] if ragged else logits[:, -1], keepdim=True)
@@ -115,6 +126,8 @@ def run(mode: str, args) -> dict:
         for _ in range(args.output_length - 1):
             t1 = time.perf_counter()
             if pages is not None:  # room for this step's token, from host-side counters
+                if trim is not None:
+                    pages.trim([max(0, n - trim + 1) for n in held])
                 held = [n + 1 for n in held]
                 pages.reserve(held)
             logits = fwd(tok, pos)
@@ -156,6 +169,8 @@ def run(mode: str, args) -> dict:
                                   for c in b.attn.kv_cache.buffers()) / 2 ** 30, 3),  # scale buffers included
         "kv_page_size": args.kv_page_size, "kv_num_pages": None if pages is None else pages.num_pages,
         "kv_pages_in_use": None if pages is None else pages.pages_in_use,
+        "kv_pages_peak": None if pages is None else pages.peak_pages_in_use,  # of the last iteration
+        "sliding_window": cfg.sliding_window_size,
         "memory_allocated_gib": round(torch.cuda.memory_allocated(device) / 2 ** 30, 3),  # held after the last step
         "max_memory_allocated_gib": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 3),
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
@@ -185,7 +200,12 @@ def main(argv=None):
                    help="pages per pool of a paged cache (default: what the static cache would hold)")
     p.add_argument("--prefill-chunk", type=int, default=None,
                    help="run the prompt in slices of at most this many columns at 2-D positions (chunked prefill)")
+    p.add_argument("--sliding-window", type=int, default=None,
+                   help="a sliding window of this many keys on every layer (overrides the model's config); with a paged "
+                        "cache the pages below the window go back to the pool")
     args = p.parse_args(argv)
+    if args.sliding_window is not None and args.sliding_window < 1:
+        p.error("--sliding-window must be >= 1")
     if args.kv_num_pages is not None and args.kv_page_size is None:
         p.error("--kv-num-pages needs --kv-page-size")
     if args.prefill_chunk is not None and args.prefill_chunk < 1:

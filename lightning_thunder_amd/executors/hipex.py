@@ -1031,6 +1031,10 @@ hip_qkv_rope_cache_slots_s8.written_args = (7, 8, 9, 10)
 _KV_PAGED_GATHER_IDS = ("custom_op.lta::kv_paged_gather", "custom_op.custom_op_impl_custom_op_lta_kv_paged_gather")
 _KV_PAGED_MASK_IDS = ("custom_op.lta::kv_paged_mask", "custom_op.custom_op_impl_custom_op_lta_kv_paged_mask")
 _KV_POSITION_MASK_IDS = ("custom_op.lta::kv_position_mask", "custom_op.custom_op_impl_custom_op_lta_kv_position_mask")
+# the same two masks under a sliding window (a trailing ``window``): read wherever those are
+_KV_WINDOW_MASK_IDS = ("custom_op.lta::kv_window_mask", "custom_op.custom_op_impl_custom_op_lta_kv_window_mask")
+_KV_PAGED_WINDOW_MASK_IDS = ("custom_op.lta::kv_paged_window_mask",
+                             "custom_op.custom_op_impl_custom_op_lta_kv_paged_window_mask")
 _CACHE_WRITES = ("index_copy_inplace", "scatter_rows_inplace")  # shared positions / one position per token
 _KV8_QUANTISE_IDS = ("custom_op.lta::kv8_quantise_rows", "custom_op.custom_op_impl_custom_op_lta_kv8_quantise_rows")
 _KV8_DEQUANTISE_IDS = ("custom_op.lta::kv8_dequantise_rows",
@@ -1053,6 +1057,30 @@ def _kv_paged_fusion_off() -> bool:
     """LTA_KV_PAGED_FUSION=0 keeps a paged cache's slot writes, page gathers and mask as the separate operations the
     model spells (A/B against the slot-writing RoPE and the paged mode of the decode kernels)."""
     return os.environ.get("LTA_KV_PAGED_FUSION", "1") == "0"
+
+
+def _kv_window_fusion_off() -> bool:
+    """LTA_KV_WINDOW_FUSION=0 keeps the masks of a model's sliding-window layers (``lta::kv_window_mask``,
+    ``lta::kv_paged_window_mask``) and the masked kernels that read them (A/B against the window mode of the decode
+    and prefill kernels); the layers without a window are fused as ever."""
+    return os.environ.get("LTA_KV_WINDOW_FUSION", "1") == "0"
+
+
+def _window_of(mask_bsym, names):
+    """``(operands by name, window)`` of a position or paged mask: window None for the plain mask; None instead of
+    the pair for a window mask that is switched off or whose window is not a plain int >= 1."""
+    if mask_bsym.sym.id not in (*_KV_WINDOW_MASK_IDS, *_KV_PAGED_WINDOW_MASK_IDS):
+        return operands(mask_bsym, names), None
+    p = operands(mask_bsym, (*names, "window"))
+    w = p["window"]
+    if _kv_window_fusion_off() or isinstance(w, (Proxy, bool)) or not isinstance(w, int) or w < 1:
+        return None
+    return p, w
+
+
+def _window_form(op, window):
+    """``(operator, its operands between the key selector and scale)`` for a fused form under ``window``."""
+    return (op, ()) if window is None else (_WINDOW_FORMS[op], (window,))
 
 
 def _ints_of(args):
@@ -1300,14 +1328,21 @@ def _fuse_kv_position_reads(trace):
     """``mask = kv_position_mask(pos, S); hip_decode_attn(q, k, v, mask, False, scale)`` with ``S`` the keys' and
     ``pos`` int64 ``[B, T]`` -> ``hip_decode_attn_pos(q, k, v, pos, scale)``: the kernel takes every row's key count
     from its position, reads no mask and splits the row's live keys over all of its workgroups.  The mask is shared
-    by the layers of a step: it must be read by such attentions only, and is dropped with the last of them."""
+    by the layers of a step: it must be read by such attentions only, and is dropped with the last of them.
+
+    ``mask = kv_window_mask(pos, S, window)`` (the sliding-window layers of a step; a model with both kinds of layer
+    holds both masks, each dropped with its own readers) -> ``hip_decode_attn_pos_win(q, k, v, pos, window, scale)``;
+    LTA_KV_WINDOW_FUSION=0 leaves that mask and its readers alone."""
     if _kv_pos_fusion_off():
         return trace
     rw = Rewrite(trace, ex)
     for m, b in enumerate(rw.bsyms):
-        if b.sym.id not in _KV_POSITION_MASK_IDS or rw.touched(m):
+        if b.sym.id not in (*_KV_POSITION_MASK_IDS, *_KV_WINDOW_MASK_IDS) or rw.touched(m):
             continue
-        p = operands(b, ("input_pos", "S"))
+        pw = _window_of(b, ("input_pos", "S"))
+        if pw is None:
+            continue
+        p, window = pw
         pos, S, mask = p["input_pos"], p["S"], b.output
         if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or pos.ndim != 2 or isinstance(S, TensorProxy):
             continue
@@ -1326,8 +1361,9 @@ def _fuse_kv_position_reads(trace):
             found.append((i, a, o))
         if not found or len(found) != len(readers):
             continue
+        op, win = _window_form(hip_decode_attn_pos, window)
         for i, a, o in found:
-            rw.replace(i, hip_decode_attn_pos.bind(o["q"], o["k"], o["v"], pos, o["scale"], output=a.output))
+            rw.replace(i, op.bind(o["q"], o["k"], o["v"], pos, *win, o["scale"], output=a.output))
         rw.drop(m)
     return rw.finish(f"hipex: {rw.replaced} decode attention(s) take their key counts from the positions")
 
@@ -1343,16 +1379,18 @@ def _fuse_kv8_reads(trace):
     must be of one kind, and nothing may write a byte or scale cache in place between its dequantise and
     the attention.
 
-    ``hip_decode_attn_pos`` folds the same chains into ``hip_decode_attn_kv8_pos`` / ``hip_decode_attn_kv8s_pos``."""
+    ``hip_decode_attn_pos`` folds the same chains into ``hip_decode_attn_kv8_pos`` / ``hip_decode_attn_kv8s_pos``,
+    ``hip_decode_attn_pos_win`` into their ``_win`` forms."""
     if _kv8_fusion_off():
         return trace
     rw = Rewrite(trace, ex)
     for i, b in enumerate(rw.bsyms):
-        if b.sym is not hip_decode_attn and b.sym is not hip_decode_attn_pos:
+        if b.sym not in (hip_decode_attn, hip_decode_attn_pos, hip_decode_attn_pos_win):
             continue
-        by_pos = b.sym is hip_decode_attn_pos
+        by_pos = b.sym is not hip_decode_attn
         p = operands(b)
         q = p["q"]
+        win = (p["window"],) if b.sym is hip_decode_attn_pos_win else ()
         for op, resolve in (((hip_decode_attn_kv8s, hip_decode_attn_kv8s_pos)[by_pos], _kv8_rows_dequantised),
                             ((hip_decode_attn_kv8, hip_decode_attn_kv8_pos)[by_pos], _e4m3_dequantised)):
             rk, rv = resolve(rw, p["k"], q.dtype), resolve(rw, p["v"], q.dtype)
@@ -1366,7 +1404,9 @@ def _fuse_kv8_reads(trace):
         if any(first < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
                for c in caches for j in rw.consumers(c)):
             continue
-        rest = (p["pos"], p["scale"]) if by_pos else (p["mask"], p["causal"], p["scale"])
+        rest = (p["pos"], *win, p["scale"]) if by_pos else (p["mask"], p["causal"], p["scale"])
+        if win:
+            op = _WINDOW_FORMS[op]
         rw.replace(i, op.bind(q, *caches, *rest, output=b.output))
         for _, _, links in (rk, rv):
             for j in links:
@@ -1399,7 +1439,10 @@ def _fuse_kv_paged_reads(trace):
     Every cache operand must be a gather read once, all at one table and page size, the mask a ``kv_paged_mask`` of
     that table, page size and int64 ``pos`` ``[B, T]``, and ``causal`` false; nothing may write a pool in place
     between its gather and the attention.  The gathers are dropped, and the mask with its last reader, when nothing
-    else reads it.  LTA_KV_PAGED_FUSION=0 turns the pass off."""
+    else reads it.  LTA_KV_PAGED_FUSION=0 turns the pass off.
+
+    Under ``kv_paged_window_mask(pos, table, page, num_pages, window)`` the same, into the ``_win`` forms with
+    ``window`` ahead of ``scale``; LTA_KV_WINDOW_FUSION=0 leaves those attentions and their mask alone."""
     if _kv_paged_fusion_off():
         return trace
     rw = Rewrite(trace, ex)
@@ -1416,9 +1459,13 @@ def _fuse_kv_paged_reads(trace):
         if p["causal"] or not isinstance(mask, TensorProxy):
             continue
         m = rw.producer(mask)
-        if m is None or rw.touched(m) or rw.bsyms[m].sym.id not in _KV_PAGED_MASK_IDS:
+        if m is None or rw.touched(m) or rw.bsyms[m].sym.id not in (*_KV_PAGED_MASK_IDS, *_KV_PAGED_WINDOW_MASK_IDS):
             continue
-        pm = operands(rw.bsyms[m], ("pos", "table", "page_size", "num_pages"))
+        pw = _window_of(rw.bsyms[m], ("pos", "table", "page_size", "num_pages"))
+        if pw is None:
+            continue
+        pm, window = pw
+        op, win = _window_form(op, window)
         pos, table = pm["pos"], pm["table"]
         if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or not isinstance(table, TensorProxy):
             continue
@@ -1433,8 +1480,8 @@ def _fuse_kv_paged_reads(trace):
         if any(g[3] < j < i and OpTags.IN_PLACE in (rw.bsyms[j].sym.tags or ())
                for g in gathers for j in rw.consumers(g[0])):
             continue
-        rw.replace(i, op.bind(q, *(g[0] for g in gathers), pos, table, pm["page_size"], pm["num_pages"], p["scale"],
-                              output=b.output))
+        rw.replace(i, op.bind(q, *(g[0] for g in gathers), pos, table, pm["page_size"], pm["num_pages"], *win,
+                              p["scale"], output=b.output))
         rw.drop(*(g[3] for g in gathers))
         masks.add(m)
     for m in masks:  # one mask serves the layers of a step
@@ -1465,7 +1512,10 @@ def _fuse_kv_prefill_reads(trace):
     dequantises the gather of a pool).  Nothing may write a cache or pool in place between the first of those links
     and the attention.  The links are dropped when nothing else reads them, the mask (one serves the layers of a
     step) with its last reader.  Anything else stays as it is: a read LSE, ``causal``, dropout, a float mask, another
-    head dim, k and v of different kinds, the 1-D ``input_pos`` route (``mask_cache.index_select``)."""
+    head dim, k and v of different kinds, the 1-D ``input_pos`` route (``mask_cache.index_select``).
+
+    ``kv_window_mask`` / ``kv_paged_window_mask`` (the sliding-window layers) are read the same way, into the ``_win``
+    forms with ``window`` ahead of ``scale``; LTA_KV_WINDOW_FUSION=0 leaves those attentions and their masks alone."""
     if _kv_prefill_fusion_off():
         return trace
     rw = Rewrite(trace, ex)
@@ -1488,21 +1538,23 @@ def _fuse_kv_prefill_reads(trace):
         if m is None or rw.touched(m):
             continue
         mb = rw.bsyms[m]
-        paged = mb.sym.id in _KV_PAGED_MASK_IDS
+        paged = mb.sym.id in (*_KV_PAGED_MASK_IDS, *_KV_PAGED_WINDOW_MASK_IDS)
+        if not paged and mb.sym.id not in (*_KV_POSITION_MASK_IDS, *_KV_WINDOW_MASK_IDS):
+            continue
+        pw = _window_of(mb, ("pos", "table", "page_size", "num_pages") if paged else ("input_pos", "S"))
+        if pw is None:
+            continue
+        pm, window = pw
         if paged:
-            pm = operands(mb, ("pos", "table", "page_size", "num_pages"))
             pos, table = pm["pos"], pm["table"]
             if _kv_paged_fusion_off() or not isinstance(table, TensorProxy):
                 continue
             if any(isinstance(pm[n], Proxy) for n in ("page_size", "num_pages")):
                 continue
-        elif mb.sym.id in _KV_POSITION_MASK_IDS:
-            pm = operands(mb, ("input_pos", "S"))
+        else:
             pos = pm["input_pos"]
             if _kv_pos_fusion_off() or isinstance(pm["S"], Proxy) or k.ndim != 4 or k.shape[2] != int(pm["S"]):
                 continue
-        else:
-            continue
         if not isinstance(pos, TensorProxy) or pos.dtype != torch.int64 or pos.ndim != 2:
             continue
         if tuple(pos.shape) != (q.shape[0], q.shape[2]):
@@ -1535,7 +1587,8 @@ def _fuse_kv_prefill_reads(trace):
                for c in caches for j in rw.consumers(c)):
             continue
         rest = (pos, table, pm["page_size"], pm["num_pages"]) if paged else (pos,)
-        rw.replace(i, ops[kind][paged].bind(q, *caches, *rest, p["scale"], output=b.output[0]))
+        op, win = _window_form(ops[kind][paged], window)
+        rw.replace(i, op.bind(q, *caches, *rest, *win, p["scale"], output=b.output[0]))
         for chain in chains:
             for j in chain:
                 # a link goes when its only reader was the attention or a link just dropped (a scaled paged cache has
@@ -2331,16 +2384,18 @@ def _decode_attn_kv8_meta(q, k8, v8, mask, causal, scale):
     return TensorProxy(like=q)
 
 
-def _decode_attn_e4m3_run(q, caches, selector, scale, supported, kernel, dequantise):
+def _decode_attn_e4m3_run(q, caches, selector, scale, supported, kernel, dequantise, window=None):
     """Decode attention over e4m3 ``caches`` in operator order (k8, v8, then scale caches), for keys chosen by
     ``selector`` = (mask, causal) or (pos,): ``kernel`` where ``supported`` takes the operands, else (more query
     rows or a head dim the e4m3 kernel does not take) the program as the model spells it,
-    ``dequantise(<a cache's operands>, dtype)`` and the 16-bit operator."""
+    ``dequantise(<a cache's operands>, dtype)`` and the 16-bit operator.  ``window``: the position forms' sliding
+    window."""
     by_pos = len(selector) == 1
+    win = {} if window is None else {"window": window}
     if supported(q, *caches, *(selector if by_pos else ())):
-        return kernel(q, *caches, *selector, scale)
+        return kernel(q, *caches, *selector, scale, **win)
     plain = _decode_attn_pos_impl if by_pos else _decode_attn_impl
-    return plain(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), *selector, scale)
+    return plain(q, dequantise(*caches[0::2], q.dtype), dequantise(*caches[1::2], q.dtype), *selector, scale, **win)
 
 
 def _decode_attn_kv8_impl(q, k8, v8, mask, causal, scale):
@@ -2375,29 +2430,35 @@ def _decode_attn_pos_meta(q, k, v, pos, scale):
     return TensorProxy(like=q)
 
 
-def _decode_attn_pos_impl(q, k, v, pos, scale):
+def _position_mask(pos, S, window=None):
+    """The mask the position forms stand for: ``position_mask``, under a sliding window ``window_mask``."""
+    from ..ops.kv_rows import position_mask, window_mask
+
+    return position_mask(pos, S) if window is None else window_mask(pos, S, window)
+
+
+def _decode_attn_pos_impl(q, k, v, pos, scale, window=None):
     from ..ops.attention import decode_attn, decode_attn_pos, decode_attn_pos_supported
-    from ..ops.kv_rows import position_mask
 
     if decode_attn_pos_supported(q, k, v, pos):
-        return decode_attn_pos(q, k, v, pos, scale)
-    return decode_attn(q, k, v, position_mask(pos, k.shape[2]), False, scale)
+        return decode_attn_pos(q, k, v, pos, scale, window=window)
+    return decode_attn(q, k, v, _position_mask(pos, k.shape[2], window), False, scale)
 
 
-def _decode_attn_kv8_pos_impl(q, k8, v8, pos, scale):
+def _decode_attn_kv8_pos_impl(q, k8, v8, pos, scale, window=None):
     from ..ops.attention import decode_attn_kv8_pos, decode_attn_kv8_pos_supported
     from ..ops.kv8 import e4m3_values
 
     return _decode_attn_e4m3_run(q, (k8, v8), (pos,), scale, decode_attn_kv8_pos_supported, decode_attn_kv8_pos,
-                                 e4m3_values)
+                                 e4m3_values, window)
 
 
-def _decode_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale):
+def _decode_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale, window=None):
     from ..ops.attention import decode_attn_kv8s_pos, decode_attn_kv8s_pos_supported
     from ..ops.kv8 import dequantise_rows
 
     return _decode_attn_e4m3_run(q, (k8, v8, k_scale, v_scale), (pos,), scale, decode_attn_kv8s_pos_supported,
-                                 decode_attn_kv8s_pos, dequantise_rows)
+                                 decode_attn_kv8s_pos, dequantise_rows, window)
 
 
 hip_decode_attn_pos = ex.register_operator("hip_decode_attn_pos", meta=_decode_attn_pos_meta, fn=_decode_attn_pos_impl)
@@ -2413,37 +2474,41 @@ def _decode_attn_paged_meta(q, k, v, pos, table, page_size, num_pages, scale):
     return TensorProxy(like=q)
 
 
-def _paged_selector(caches, pos, table, page_size, num_pages):
-    """The operands of the mask form: every pool's logical cache and the paged mask."""
-    from ..ops.kv_pages import gather_pages, paged_mask
+def _paged_selector(caches, pos, table, page_size, num_pages, window=None):
+    """The operands of the mask form: every pool's logical cache and the paged mask (under a sliding window the paged
+    window mask)."""
+    from ..ops.kv_pages import gather_pages, paged_mask, paged_window_mask
 
-    return [gather_pages(c, table, page_size) for c in caches], paged_mask(pos, table, page_size, num_pages)
+    mask = paged_mask(pos, table, page_size, num_pages) if window is None else \
+        paged_window_mask(pos, table, page_size, num_pages, window)
+    return [gather_pages(c, table, page_size) for c in caches], mask
 
 
-def _decode_attn_paged_impl(q, k, v, pos, table, page_size, num_pages, scale):
+def _decode_attn_paged_impl(q, k, v, pos, table, page_size, num_pages, scale, window=None):
     from ..ops.attention import decode_attn_paged, decode_attn_paged_supported
 
     if decode_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
-        return decode_attn_paged(q, k, v, pos, table, page_size, num_pages, scale)
-    caches, mask = _paged_selector((k, v), pos, table, page_size, num_pages)
+        return decode_attn_paged(q, k, v, pos, table, page_size, num_pages, scale, window=window)
+    caches, mask = _paged_selector((k, v), pos, table, page_size, num_pages, window)
     return _decode_attn_impl(q, *caches, mask, False, scale)
 
 
-def _decode_attn_kv8_paged_impl(q, k8, v8, pos, table, page_size, num_pages, scale):
+def _decode_attn_kv8_paged_impl(q, k8, v8, pos, table, page_size, num_pages, scale, window=None):
     from ..ops.attention import decode_attn_kv8_paged, decode_attn_kv8_paged_supported
 
     if decode_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
-        return decode_attn_kv8_paged(q, k8, v8, pos, table, page_size, num_pages, scale)
-    caches, mask = _paged_selector((k8, v8), pos, table, page_size, num_pages)
+        return decode_attn_kv8_paged(q, k8, v8, pos, table, page_size, num_pages, scale, window=window)
+    caches, mask = _paged_selector((k8, v8), pos, table, page_size, num_pages, window)
     return _decode_attn_kv8_impl(q, *caches, mask, False, scale)
 
 
-def _decode_attn_kv8s_paged_impl(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale):
+def _decode_attn_kv8s_paged_impl(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale, window=None):
     from ..ops.attention import decode_attn_kv8s_paged, decode_attn_kv8s_paged_supported
 
     if decode_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
-        return decode_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale)
-    caches, mask = _paged_selector((k8, v8, k_scale, v_scale), pos, table, page_size, num_pages)
+        return decode_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale,
+                                      window=window)
+    caches, mask = _paged_selector((k8, v8, k_scale, v_scale), pos, table, page_size, num_pages, window)
     return _decode_attn_kv8s_impl(q, *caches, mask, False, scale)
 
 
@@ -2460,32 +2525,31 @@ hip_decode_attn_kv8s_paged = ex.register_operator(
 # The prefill forms (csrc/prefill_attention.hip): the position and paged forms above for any number of query rows, in
 # place of the masked flash attention over the gathered / dequantised cache.  Each runs its kernel where
 # ``*_supported`` takes the operands, else the program as the model spells it.
-def _prefill_attn_pos_impl(q, k, v, pos, scale):
+def _prefill_attn_pos_impl(q, k, v, pos, scale, window=None):
     from ..ops.attention import attn_fwd, prefill_attn_pos, prefill_attn_pos_supported
-    from ..ops.kv_rows import position_mask
 
     if prefill_attn_pos_supported(q, k, v, pos):
-        return prefill_attn_pos(q, k, v, pos, scale)
-    return attn_fwd(q, k, v, False, scale, mask=position_mask(pos, k.shape[2]))[0]
+        return prefill_attn_pos(q, k, v, pos, scale, window=window)
+    return attn_fwd(q, k, v, False, scale, mask=_position_mask(pos, k.shape[2], window))[0]
 
 
-def _prefill_attn_kv8_pos_impl(q, k8, v8, pos, scale):
+def _prefill_attn_kv8_pos_impl(q, k8, v8, pos, scale, window=None):
     from ..ops.attention import prefill_attn_kv8_pos, prefill_attn_kv8_pos_supported
     from ..ops.kv8 import e4m3_values
 
     if prefill_attn_kv8_pos_supported(q, k8, v8, pos):
-        return prefill_attn_kv8_pos(q, k8, v8, pos, scale)
-    return _prefill_attn_pos_impl(q, e4m3_values(k8, q.dtype), e4m3_values(v8, q.dtype), pos, scale)
+        return prefill_attn_kv8_pos(q, k8, v8, pos, scale, window=window)
+    return _prefill_attn_pos_impl(q, e4m3_values(k8, q.dtype), e4m3_values(v8, q.dtype), pos, scale, window)
 
 
-def _prefill_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale):
+def _prefill_attn_kv8s_pos_impl(q, k8, v8, k_scale, v_scale, pos, scale, window=None):
     from ..ops.attention import prefill_attn_kv8s_pos, prefill_attn_kv8s_pos_supported
     from ..ops.kv8 import dequantise_rows
 
     if prefill_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
-        return prefill_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale)
+        return prefill_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale, window=window)
     return _prefill_attn_pos_impl(q, dequantise_rows(k8, k_scale, q.dtype), dequantise_rows(v8, v_scale, q.dtype), pos,
-                                  scale)
+                                  scale, window)
 
 
 def _prefill_attn_unpaged(q, caches, mask, scale):
@@ -2502,28 +2566,29 @@ def _prefill_attn_unpaged(q, caches, mask, scale):
     return attn_fwd(q, k, v, False, scale, mask=mask)[0]
 
 
-def _prefill_attn_paged_impl(q, k, v, pos, table, page_size, num_pages, scale):
+def _prefill_attn_paged_impl(q, k, v, pos, table, page_size, num_pages, scale, window=None):
     from ..ops.attention import prefill_attn_paged, prefill_attn_paged_supported
 
     if prefill_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
-        return prefill_attn_paged(q, k, v, pos, table, page_size, num_pages, scale)
-    return _prefill_attn_unpaged(q, *_paged_selector((k, v), pos, table, page_size, num_pages), scale)
+        return prefill_attn_paged(q, k, v, pos, table, page_size, num_pages, scale, window=window)
+    return _prefill_attn_unpaged(q, *_paged_selector((k, v), pos, table, page_size, num_pages, window), scale)
 
 
-def _prefill_attn_kv8_paged_impl(q, k8, v8, pos, table, page_size, num_pages, scale):
+def _prefill_attn_kv8_paged_impl(q, k8, v8, pos, table, page_size, num_pages, scale, window=None):
     from ..ops.attention import prefill_attn_kv8_paged, prefill_attn_kv8_paged_supported
 
     if prefill_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
-        return prefill_attn_kv8_paged(q, k8, v8, pos, table, page_size, num_pages, scale)
-    return _prefill_attn_unpaged(q, *_paged_selector((k8, v8), pos, table, page_size, num_pages), scale)
+        return prefill_attn_kv8_paged(q, k8, v8, pos, table, page_size, num_pages, scale, window=window)
+    return _prefill_attn_unpaged(q, *_paged_selector((k8, v8), pos, table, page_size, num_pages, window), scale)
 
 
-def _prefill_attn_kv8s_paged_impl(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale):
+def _prefill_attn_kv8s_paged_impl(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale, window=None):
     from ..ops.attention import prefill_attn_kv8s_paged, prefill_attn_kv8s_paged_supported
 
     if prefill_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
-        return prefill_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale)
-    caches, mask = _paged_selector((k8, v8, k_scale, v_scale), pos, table, page_size, num_pages)
+        return prefill_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale,
+                                       window=window)
+    caches, mask = _paged_selector((k8, v8, k_scale, v_scale), pos, table, page_size, num_pages, window)
     return _prefill_attn_unpaged(q, caches, mask, scale)
 
 
@@ -2542,6 +2607,46 @@ hip_prefill_attn_kv8s_paged = ex.register_operator(
     "hip_prefill_attn_kv8s_paged",
     meta=lambda q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, scale: TensorProxy(like=q),
     fn=_prefill_attn_kv8s_paged_impl)
+
+
+# The window forms (a sliding window of ``window`` keys per row, its own included): every position / paged form above
+# with ``window`` ahead of ``scale``, on the ``*_win`` entries of the two kernels.
+def _pos_win_meta(q, k, v, pos, window, scale):
+    return TensorProxy(like=q)
+
+
+def _kv8s_pos_win_meta(q, k8, v8, k_scale, v_scale, pos, window, scale):
+    return TensorProxy(like=q)
+
+
+def _paged_win_meta(q, k, v, pos, table, page_size, num_pages, window, scale):
+    return TensorProxy(like=q)
+
+
+def _kv8s_paged_win_meta(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages, window, scale):
+    return TensorProxy(like=q)
+
+
+def _windowed(impl):
+    """``impl(..., scale, window)`` as the operator orders its operands: ``(..., window, scale)``."""
+    def run(*a):
+        return impl(*a[:-2], a[-1], a[-2])
+
+    return run
+
+
+_WINDOW_FORMS = {}  # a position / paged operator -> its window form
+for _kind, _impls in (("decode", (_decode_attn_pos_impl, _decode_attn_kv8_pos_impl, _decode_attn_kv8s_pos_impl,
+                                  _decode_attn_paged_impl, _decode_attn_kv8_paged_impl, _decode_attn_kv8s_paged_impl)),
+                      ("prefill", (_prefill_attn_pos_impl, _prefill_attn_kv8_pos_impl, _prefill_attn_kv8s_pos_impl,
+                                   _prefill_attn_paged_impl, _prefill_attn_kv8_paged_impl,
+                                   _prefill_attn_kv8s_paged_impl))):
+    for _form, _meta, _impl in zip(("pos", "kv8_pos", "kv8s_pos", "paged", "kv8_paged", "kv8s_paged"),
+                                   (_pos_win_meta, _pos_win_meta, _kv8s_pos_win_meta, _paged_win_meta, _paged_win_meta,
+                                    _kv8s_paged_win_meta), _impls):
+        _name = f"hip_{_kind}_attn_{_form}"
+        _WINDOW_FORMS[globals()[_name]] = globals()[_name + "_win"] = ex.register_operator(
+            _name + "_win", meta=_meta, fn=_windowed(_impl))
 
 
 def _broadcastable(shape, target) -> bool:

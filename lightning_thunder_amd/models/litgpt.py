@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field, replace
-from typing import Optional
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -22,8 +22,9 @@ import torch.utils.checkpoint
 import torch.nn.functional as F
 
 from ..ops.kv8 import kv8_dequantise_rows, kv8_quantise_rows
-from ..ops.kv_pages import PageTable, check_page_size, kv_page_slots, kv_paged_gather, kv_paged_mask
-from ..ops.kv_rows import kv_position_mask
+from ..ops.kv_pages import (PageTable, check_page_size, kv_page_slots, kv_paged_gather, kv_paged_mask,
+                            kv_paged_window_mask)
+from ..ops.kv_rows import kv_position_mask, kv_window_mask
 
 
 @dataclass
@@ -55,8 +56,24 @@ class Config:
     # Gemma: token embeddings scaled by sqrt(n_embd), RMSNorm scale (1 + weight)
     scale_embeddings: bool = False
     norm_unit_offset: bool = False
+    # Sliding-window attention (Mistral, Phi-3, Gemma-2): the token at position p sees key j iff p - W < j <= p, that
+    # is W keys, itself included (the Mistral / HF convention; LitGPT's own mask keeps W + 1).
+    # ``sliding_window_indices`` holds one 0 / 1 per layer (1: the layer is windowed); all ones when only the size is set.
+    sliding_window_size: Optional[int] = None
+    sliding_window_indices: Optional[List[int]] = None
 
     def __post_init__(self):
+        if self.sliding_window_indices is not None and len(self.sliding_window_indices) != self.n_layer:
+            raise ValueError(f"Config: sliding_window_indices has {len(self.sliding_window_indices)} entries for "
+                             f"{self.n_layer} layers")
+        if self.sliding_window_size is None:
+            self.sliding_window_indices = None
+        else:
+            W = self.sliding_window_size
+            if isinstance(W, bool) or not isinstance(W, int) or W < 1:
+                raise ValueError(f"Config: sliding_window_size must be an int >= 1 or None, got {W!r}")
+            if self.sliding_window_indices is None:
+                self.sliding_window_indices = [1] * self.n_layer
         if self.head_size is None:
             self.head_size = self.n_embd // self.n_head
         if self.padded_vocab_size is None:
@@ -70,7 +87,23 @@ class Config:
     @classmethod
     def from_name(cls, name: str, **kwargs) -> "Config":
         base = name_to_config[name]
+        if "sliding_window_indices" not in kwargs and base.sliding_window_indices is not None \
+                and all(base.sliding_window_indices):
+            kwargs["sliding_window_indices"] = None  # "every layer" follows an n_layer given here
         return replace(base, **kwargs)
+
+    def layer_window(self, block_idx: int) -> Optional[int]:
+        """The window of layer ``block_idx``, None for a layer that attends every earlier key."""
+        if self.sliding_window_size is None or not self.sliding_window_indices[block_idx]:
+            return None
+        return self.sliding_window_size
+
+    @property
+    def uniform_window(self) -> Optional[int]:
+        """The window when every layer has it (only then may a paged cache give up the pages below it), else None."""
+        if self.sliding_window_size is None or not all(self.sliding_window_indices):
+            return None
+        return self.sliding_window_size
 
     @property
     def qkv_size(self) -> int:
@@ -94,7 +127,7 @@ configs = [
            n_embd=2048, n_query_groups=8, intermediate_size=8192, rope_base=500000, tie_embeddings=True),
     # Mistral
     Config(name="Mistral-7B-v0.1", block_size=4096, vocab_size=32000, padded_vocab_size=32000, n_layer=32, n_head=32,
-           n_embd=4096, n_query_groups=8, intermediate_size=14336),
+           n_embd=4096, n_query_groups=8, intermediate_size=14336, sliding_window_size=4096),
     Config(name="Mistral-7B-v0.2", block_size=32768, vocab_size=32000, padded_vocab_size=32000, n_layer=32, n_head=32,
            n_embd=4096, n_query_groups=8, intermediate_size=14336, rope_base=1000000),
     # Google Gemma (the reference's multi-model chart and GemmaMLP target, BASELINE.md:26):
@@ -121,6 +154,12 @@ configs = [
            block_size=128),
     Config(name="llama3-like", vocab_size=320, padded_vocab_size=320, n_layer=2, n_head=4, n_embd=64, n_query_groups=2,
            intermediate_size=96, block_size=128, rope_base=500000),
+    # llama3-like under a 24-key sliding window: on every layer (Mistral), on the even layers only (Gemma-2)
+    Config(name="mistral-like", vocab_size=320, padded_vocab_size=320, n_layer=2, n_head=4, n_embd=64, n_query_groups=2,
+           intermediate_size=96, block_size=128, rope_base=500000, sliding_window_size=24),
+    Config(name="gemma2-like", vocab_size=320, padded_vocab_size=320, n_layer=2, n_head=4, n_embd=64, n_query_groups=2,
+           intermediate_size=96, block_size=128, rope_base=500000, sliding_window_size=24,
+           sliding_window_indices=[1, 0]),
     Config(name="gpt-neox-like", vocab_size=320, padding_multiple=64, n_layer=2, n_head=4, n_embd=64, block_size=128,
            norm_class_name="LayerNorm", mlp_class_name="GptNeoxMLP", bias=True, parallel_residual=True,
            rotary_percentage=0.25),
@@ -368,6 +407,8 @@ class CausalSelfAttention(nn.Module):
                 raise TypeError("call model.set_kv_cache(...) before passing input_pos")
             k, v = self.kv_cache(input_pos, k, v)
             y = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, enable_gqa=c.n_query_groups != c.n_head)
+        elif mask is not None:  # a windowed layer over more tokens than its window: the band mask
+            y = F.scaled_dot_product_attention(q, k, v, attn_mask=mask, enable_gqa=c.n_query_groups != c.n_head)
         else:
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=c.n_query_groups != c.n_head)
         y = y.transpose(1, 2).reshape(B, T, c.n_head * c.head_size)
@@ -462,8 +503,9 @@ class LLaMAMoE(nn.Module):
 
 
 class Block(nn.Module):
-    def __init__(self, config: Config):
+    def __init__(self, config: Config, block_idx: int = 0):
         super().__init__()
+        self.sliding_window = config.layer_window(block_idx)  # None: the layer attends every earlier key
         self.norm_1 = _norm(config, config.n_embd)
         self.attn = CausalSelfAttention(config)
         self.norm_2 = None if config.shared_attention_norm else _norm(config, config.n_embd)
@@ -498,7 +540,7 @@ class GPT(nn.Module):
         self.transformer = nn.ModuleDict(
             dict(
                 wte=nn.Embedding(config.padded_vocab_size, config.n_embd),
-                h=nn.ModuleList(Block(config) for _ in range(config.n_layer)),
+                h=nn.ModuleList(Block(config, i) for i in range(config.n_layer)),
                 ln_f=_norm(config, config.n_embd),
             )
         )
@@ -508,6 +550,7 @@ class GPT(nn.Module):
         self.register_buffer("cos", torch.empty(0), persistent=False)
         self.register_buffer("sin", torch.empty(0), persistent=False)
         self.mask_cache: Optional[torch.Tensor] = None
+        self.window_mask_cache: Optional[torch.Tensor] = None  # the band mask of the windowed layers (1-D input_pos)
         self.kv_pages: Optional[PageTable] = None  # the allocator of a paged KV cache (set_kv_cache(page_size=...))
         self.page_table: Optional[torch.Tensor] = None  # its device block table, shared by all layers
         self._rope_seq = 0
@@ -556,7 +599,7 @@ class GPT(nn.Module):
             max_seq_length = max_pages * page_size
             if self.cos.numel() == 0 or self.cos.shape[0] < max_seq_length:
                 self.set_rope_cache(max_seq_length, device=device)
-            self.mask_cache = None
+            self.mask_cache = self.window_mask_cache = None
             self.max_seq_length = max_seq_length
             return
         for block in self.transformer.h:
@@ -569,12 +612,16 @@ class GPT(nn.Module):
             self.set_rope_cache(max_seq_length, device=device)
         ones = torch.ones((max_seq_length, max_seq_length), device=device, dtype=torch.bool)
         self.mask_cache = torch.tril(ones).unsqueeze(0).unsqueeze(0)
+        W = c.sliding_window_size
+        self.window_mask_cache = None
+        if W is not None and W < max_seq_length:  # row p: keys p - W + 1 .. p
+            self.window_mask_cache = torch.triu(torch.tril(ones), diagonal=1 - W).unsqueeze(0).unsqueeze(0)
         self.max_seq_length = max_seq_length
 
     def clear_kv_cache(self) -> None:
         for block in self.transformer.h:
             block.attn.kv_cache = None
-        self.mask_cache = None
+        self.mask_cache = self.window_mask_cache = None
         self.kv_pages = self.page_table = None
 
     def forward(self, idx: torch.Tensor, input_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -582,6 +629,10 @@ class GPT(nn.Module):
         if self.cos.numel() == 0 or self.cos.shape[0] < T:
             raise RuntimeError("call model.set_rope_cache(seq_len, device) before forward")
         pages = None
+        # the windowed layers' mask, next to the global one: only where the window hides a key some row could see (a
+        # cache of more than W positions, more than W tokens without a cache); else every layer runs the global code
+        W = self.config.sliding_window_size
+        wmask = None
         if input_pos is not None and self.kv_pages is not None:  # a paged cache: slots and mask once per step
             if input_pos.dim() != 2:
                 raise TypeError("a paged KV cache takes the 2-D input_pos [B, T] (one position per token) only, "
@@ -594,6 +645,8 @@ class GPT(nn.Module):
             table = self.page_table
             slots = kv_page_slots(table, input_pos, pt.page_size, pt.num_pages * pt.page_size)
             mask = kv_paged_mask(input_pos, table, pt.page_size, pt.num_pages)
+            if W is not None and W < self.max_seq_length:
+                wmask = kv_paged_window_mask(input_pos, table, pt.page_size, pt.num_pages, W)
             pages = (slots, table)
         elif input_pos is not None and input_pos.dim() == 2:  # a ragged batch: one position per (sequence, token)
             B = idx.size(0)
@@ -601,18 +654,27 @@ class GPT(nn.Module):
             cos = self.cos.index_select(0, flat).view(B, T, -1)
             sin = self.sin.index_select(0, flat).view(B, T, -1)
             mask = kv_position_mask(input_pos, self.max_seq_length)
+            if W is not None and W < self.max_seq_length:
+                wmask = kv_window_mask(input_pos, self.max_seq_length, W)
         elif input_pos is not None:  # incremental decoding against the KV cache
             cos = self.cos.index_select(0, input_pos)
             sin = self.sin.index_select(0, input_pos)
             mask = self.mask_cache.index_select(2, input_pos)
+            if self.window_mask_cache is not None:
+                wmask = self.window_mask_cache.index_select(2, input_pos)
         else:
             cos = self.cos[:T]
             sin = self.sin[:T]
             mask = None
+            if W is not None and T > W:
+                ones = torch.ones((T, T), device=idx.device, dtype=torch.bool)
+                wmask = torch.triu(torch.tril(ones), diagonal=1 - W).unsqueeze(0).unsqueeze(0)
         x = self.transformer.wte(idx)
         if self.config.scale_embeddings:
             x = x * math.sqrt(self.config.n_embd)
+        global_mask = mask
         for block in self.transformer.h:
+            mask = wmask if wmask is not None and block.sliding_window is not None else global_mask
             if self.activation_checkpointing and input_pos is None:
                 # recompute the block's intermediates in the backward (LitGPT / benchmark_litgpt
                 # ``--checkpoint_activations``); traced as ltorch.checkpoint
@@ -725,16 +787,20 @@ def generate(model, prompt: torch.Tensor, max_new_tokens: int, *, forward=None, 
     return torch.cat(out, dim=1)
 
 
-def _chunked_prefill(forward, prompt, chunk: int, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _chunked_prefill(forward, prompt, chunk: int, lengths: Optional[torch.Tensor] = None,
+                     before_chunk=None) -> torch.Tensor:
     """The prompt ``[B, T]`` through ``forward`` in slices of at most ``chunk`` columns at the 2-D positions
     ``arange(c0, c1)``.  Returns the logits ``[B, V]`` every sequence's first new token is drawn from: those of column
-    ``lengths[b] - 1`` (``T - 1`` without ``lengths``), picked out of the chunk that holds it; no other logits are kept."""
+    ``lengths[b] - 1`` (``T - 1`` without ``lengths``), picked out of the chunk that holds it; no other logits are kept.
+    ``before_chunk(c0, c1)`` runs ahead of every slice (a paged cache under a sliding window moves its pages there)."""
     B, T = prompt.shape
     device = prompt.device
     rows = torch.arange(B, device=device)
     last = None
     for c0 in range(0, T, chunk):
         c1 = min(T, c0 + chunk)
+        if before_chunk is not None:
+            before_chunk(c0, c1)
         pos2d = torch.arange(c0, c1, device=device, dtype=torch.int64).expand(B, c1 - c0).contiguous()
         logits = forward(prompt[:, c0:c1], pos2d)
         if lengths is None:
@@ -765,7 +831,15 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
     finished get room for one more token, from host-side counters; a finished sequence receives no further page.
 
     With ``prefill_chunk`` the prefill is ``_chunked_prefill`` on either cache: slices of the padded prompt at 2-D
-    positions, after the prompts' pages are reserved; a pad token's K/V row is overwritten as above.  Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
+    positions, after the prompts' pages are reserved; a pad token's K/V row is overwritten as above.
+
+    When every layer of the model has one sliding window ``W`` (``Config.uniform_window``), a paged cache gives up the
+    pages no later row can see: before every ``reserve`` the table is trimmed to ``len_b - W + 1`` (floored at 0), with
+    ``len_b`` the position the sequence's next row sits at, per decode step and per prefill chunk, and a chunked prefill
+    reserves its pages chunk by chunk.  A sequence then holds about ``W / page_size`` pages however long it grows.  A
+    model with any global layer never trims.
+
+    Returns ``[B, Tmax + max_new_tokens]``: row b is its prompt, the new tokens
     from column ``len_b`` on, then ``pad_id``."""
     from ..ops.sampling import argmax_last, sample_last
 
@@ -797,12 +871,20 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
         # pages for the prompts; a pad token beyond its sequence's last page has no slot and falls to the sink row
         held = lengths.tolist()  # host-side counters from here on
         live = [True] * B
+        trim = getattr(getattr(model, "config", None), "uniform_window", None)  # the window pages may fall out of
         pages.reset()  # a generation starts from an empty table, as it overwrites a static cache
-        pages.reserve(held)
+        if trim is None or prefill_chunk is None:
+            pages.reserve(held)
         if prefill_chunk is None:
             logits = forward(prompt, torch.arange(T, device=device).expand(B, T).contiguous())
     if prefill_chunk is None:
         last = logits[torch.arange(B, device=device), lengths - 1]
+    elif pages is not None and trim is not None:
+        def move_pages(c0, c1):  # the chunk's rows sit at c0 .. c1 - 1; a sequence that ended earlier waits at len_b
+            pages.trim([max(0, min(c0, n) - trim + 1) for n in held])
+            pages.reserve([min(c1, n) for n in held])
+
+        last = _chunked_prefill(forward, prompt, prefill_chunk, lengths, move_pages)
     else:
         last = _chunked_prefill(forward, prompt, prefill_chunk, lengths)
     pos = lengths.clone().view(B, 1)  # where the next token of every sequence goes; advanced in place
@@ -822,6 +904,8 @@ def _generate_ragged(model, prompt, max_new_tokens, forward, temperature, top_k,
                 live = [not d for d in done.view(-1).tolist()]
         if i + 1 < max_new_tokens:
             if pages is not None:  # room for this step's token; a finished sequence gets no further page
+                if trim is not None:  # the step's row sits at position n and sees keys n - W + 1 .. n
+                    pages.trim([max(0, n - trim + 1) for n in held])
                 held = [n + 1 if alive else n for n, alive in zip(held, live)]
                 pages.reserve(held)
             logits = forward(nxt, pos)

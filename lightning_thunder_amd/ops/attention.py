@@ -387,6 +387,9 @@ for _entry, _scale_ptrs in (("lta_decode_attn", 0), ("lta_decode_attn_kv8", 0), 
     register_signature(_entry + "_pos", [*_head, c_int, c_float, c_int, c_void_p])
     # the paged entries: the position entries', then the block table, log2 of the page size and the page count
     register_signature(_entry + "_paged", [*_head, c_int, c_float, c_int, c_void_p, c_int, c_int, c_void_p])
+    # the window entries: the position / paged entries', then the window
+    register_signature(_entry + "_pos_win", [*_head, c_int, c_float, c_int, c_void_p, c_int])
+    register_signature(_entry + "_paged_win", [*_head, c_int, c_float, c_int, c_void_p, c_int, c_int, c_void_p, c_int])
 
 DECODE_MAX_QUERIES = 16
 
@@ -404,8 +407,18 @@ def decode_launch_shape(rows: int, S: int):
     return wsplit, nsplit, chunk
 
 
+def _window_arg(fn: str, window) -> tuple:
+    """The trailing argument of a ``*_win`` entry: ``()`` without a window, else ``(window,)`` for an int >= 1
+    (``ValueError`` for anything else)."""
+    if window is None:
+        return ()
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"{fn}: window must be an int >= 1 or None, got {window!r}")
+    return (min(window, 2 ** 31 - 1),)
+
+
 def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: bool = False, pos=None, scales=(),
-                   pages=None):
+                   pages=None, window: int | None = None):
     """One launch of ``entry``: a mask entry with (``mask``, ``causal``), a position entry with ``pos``.  ``scales`` =
     (k_scale, v_scale) for the scaled-e4m3 entries, whose argument list carries the two pointers after v.  The
     stride record is q, k, v (b, h, t each), then the selector's (mask b, h, t, s or pos b, t), then the scales'.
@@ -416,7 +429,14 @@ def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: 
 
     The grid comes from the capacity S in both modes (``decode_launch_shape``): positions stay on the device, so a
     hipGraph replays the launch while they advance; the kernel splits each row's live range over the ``nsplit``
-    workgroups itself."""
+    workgroups itself.
+
+    ``window`` (position and paged entries only) launches ``entry + "_win"`` with the window after the stream: row
+    (b, hq, t) attends its last ``window`` live positions only.  Without it the launch is ``entry``'s, argument for
+    argument."""
+    win = _window_arg(entry, window)
+    if win:
+        entry += "_win"
     lib = require()
     B, Hq, T, D = q.shape
     if pages is not None:
@@ -445,7 +465,7 @@ def _decode_launch(entry: str, q, k, v, scale: float | None, mask=None, causal: 
     st = (ctypes.c_int64 * len(st))(*st)
     rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *map(ptr, scales), ptr(sel), ptr(o), ptr(ws_acc),
                              ptr(ws_ml), B, Hq, Hkv, T, S, D, ctypes.cast(st, ctypes.c_void_p), *split, float(sc),
-                             int(wsplit), *tail[2:], stream_ptr(q.device))
+                             int(wsplit), *tail[2:], stream_ptr(q.device), *win)
     check(rc, entry)
     return o
 
@@ -538,31 +558,37 @@ def decode_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos) -> bool:
     return _pos_ok(q, k8, pos) and decode_attn_kv8s_supported(q, k8, v8, k_scale, v_scale)
 
 
-def decode_attn_pos(q, k, v, pos, scale: float | None = None):
+def decode_attn_pos(q, k, v, pos, scale: float | None = None, window: int | None = None):
     """Decode attention of a ragged batch: q [B, Hq, T, D] (T <= 16), k / v [B, Hkv, S, D], ``pos`` int64
     [B, T].  Row (b, hq, t) attends keys ``0 .. n-1`` with ``n = clamp(pos[b, t] + 1, 0, S)``: what
     ``decode_attn`` computes under the mask ``arange(S) <= pos[b, t]``, without the mask tensor and with the
-    row's live keys split over all of its workgroups.  ``n = 0`` gives a NaN row, like a fully masked one."""
+    row's live keys split over all of its workgroups.  ``n = 0`` gives a NaN row, like a fully masked one.
+
+    ``window`` (an int >= 1; here and on the other position / paged wrappers) is a sliding window: the row attends keys
+    ``max(0, n - window) .. n-1``, that is ``window`` keys with its own (the Mistral / HF convention; LitGPT's own mask
+    keeps ``window + 1``), what ``decode_attn`` computes under ``window_mask(pos, S, window)``; only those keys are
+    read, and on a paged cache only their table entries.  Where ``window >= n`` for every row the result is the
+    call's without a window, bit for bit.  ``None`` launches the entry without a window."""
     if not decode_attn_pos_supported(q, k, v, pos):
         raise _refusal("decode_attn_pos", q=q, k=k, v=v, pos=pos)
     q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
-    return _decode_launch("lta_decode_attn_pos", q, k, v, scale, pos=pos)
+    return _decode_launch("lta_decode_attn_pos", q, k, v, scale, pos=pos, window=window)
 
 
-def decode_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None):
+def decode_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None, window: int | None = None):
     """``decode_attn_pos`` over an unscaled e4m3 cache (the operands of ``decode_attn_kv8``)."""
     if not decode_attn_kv8_pos_supported(q, k8, v8, pos):
         raise _refusal("decode_attn_kv8_pos", q=q, k=k8, v=v8, pos=pos)
-    return _decode_launch("lta_decode_attn_kv8_pos", *_e4m3_in_place(q, k8, v8), scale, pos=pos)
+    return _decode_launch("lta_decode_attn_kv8_pos", *_e4m3_in_place(q, k8, v8), scale, pos=pos, window=window)
 
 
-def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None):
+def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None, window: int | None = None):
     """``decode_attn_pos`` over the scaled e4m3 cache (the operands of ``decode_attn_kv8s``): equals
     ``decode_attn_pos`` over the dequantised cache bit for bit, with that kernel's exclusions."""
     if not decode_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
         raise _refusal("decode_attn_kv8s_pos", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos)
     return _decode_launch("lta_decode_attn_kv8s_pos", *_e4m3_in_place(q, k8, v8), scale, pos=pos,
-                          scales=(k_scale, v_scale))
+                          scales=(k_scale, v_scale), window=window)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -611,7 +637,8 @@ def decode_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, pa
     return _paged_ok(q, k8, v8, pos, table, page_size, num_pages, torch.uint8, (k_scale, v_scale))
 
 
-def decode_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+def decode_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale: float | None = None,
+                      window: int | None = None):
     """``decode_attn_pos`` over a paged cache: k / v pools ``[Hkv, R + 1, D]``, ``table`` int64 ``[B, max_pages]``.
     Row (b, hq, t) attends the keys ``j <= pos[b, t]`` (clamped to the capacity ``S = max_pages * page_size``) whose
     table entry lies in ``[0, num_pages)``, each read at pool row ``table[b, j // page_size] * page_size + j %
@@ -619,25 +646,26 @@ def decode_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale
     if not decode_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
         raise _refusal("decode_attn_paged", q=q, k=k, v=v, pos=pos, table=table)
     return _decode_launch("lta_decode_attn_paged", _rows_in_place(q), k, v, scale, pos=pos,
-                          pages=(table, page_size, num_pages))
+                          pages=(table, page_size, num_pages), window=window)
 
 
-def decode_attn_kv8_paged(q, k8, v8, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+def decode_attn_kv8_paged(q, k8, v8, pos, table, page_size: int, num_pages: int, scale: float | None = None,
+                          window: int | None = None):
     """``decode_attn_paged`` over unscaled e4m3 pools (uint8)."""
     if not decode_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
         raise _refusal("decode_attn_kv8_paged", q=q, k=k8, v=v8, pos=pos, table=table)
     return _decode_launch("lta_decode_attn_kv8_paged", _rows_in_place(q), k8, v8, scale, pos=pos,
-                          pages=(table, page_size, num_pages))
+                          pages=(table, page_size, num_pages), window=window)
 
 
 def decode_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size: int, num_pages: int,
-                           scale: float | None = None):
+                           scale: float | None = None, window: int | None = None):
     """``decode_attn_paged`` over the scaled e4m3 pools: bytes ``[Hkv, R + 1, D]`` and scale bytes ``[Hkv, R + 1, 1]``."""
     if not decode_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
         raise _refusal("decode_attn_kv8s_paged", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos,
                        table=table)
     return _decode_launch("lta_decode_attn_kv8s_paged", _rows_in_place(q), k8, v8, scale, pos=pos,
-                          scales=(k_scale, v_scale), pages=(table, page_size, num_pages))
+                          scales=(k_scale, v_scale), pages=(table, page_size, num_pages), window=window)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -650,12 +678,18 @@ for _entry, _scale_ptrs in (("lta_prefill_attn", 0), ("lta_prefill_attn_kv8", 0)
     _head = [c_int, *[c_void_p] * (5 + _scale_ptrs), *[c_int] * 6, c_void_p, c_void_p, c_float]
     register_signature(_entry + "_pos", [*_head, c_void_p])
     register_signature(_entry + "_paged", [*_head, c_void_p, c_int, c_int, c_void_p])
+    register_signature(_entry + "_pos_win", [*_head, c_void_p, c_int])
+    register_signature(_entry + "_paged_win", [*_head, c_void_p, c_int, c_int, c_void_p, c_int])
 
 
-def _prefill_launch(entry: str, q, k, v, pos, scale: float | None, scales=(), pages=None):
+def _prefill_launch(entry: str, q, k, v, pos, scale: float | None, scales=(), pages=None, window: int | None = None):
     """One launch of the prefill entry ``entry`` (operands as ``_decode_launch`` takes them in its position mode).  O
     is stored ``[B, T, Hq, D]`` and returned as its ``[B, Hq, T, D]`` view, as ``attn_fwd`` does.  The grid comes from
-    the shapes alone: positions and table stay on the device, so the launch is capturable."""
+    the shapes alone: positions and table stay on the device, so the launch is capturable.  ``window`` launches
+    ``entry + "_win"`` with the window after the stream, as ``_decode_launch`` does."""
+    win = _window_arg(entry, window)
+    if win:
+        entry += "_win"
     lib = require()
     B, Hq, T, D = q.shape
     if pages is not None:
@@ -673,7 +707,7 @@ def _prefill_launch(entry: str, q, k, v, pos, scale: float | None, scales=(), pa
     st = (ctypes.c_int64 * len(st))(*st)
     rc = getattr(lib, entry)(dcode(q), ptr(q), ptr(k), ptr(v), *map(ptr, scales), ptr(pos), ptr(o), B, Hq, Hkv, T, S, D,
                              ctypes.cast(st, c_void_p), ctypes.cast(_strides3(o), c_void_p), float(sc), *tail[2:],
-                             stream_ptr(q.device))
+                             stream_ptr(q.device), *win)
     check(rc, entry)
     return o
 
@@ -692,32 +726,36 @@ def prefill_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos) -> bool:
     return prefill_attn_kv8_pos_supported(q, k8, v8, pos) and scale_caches_of((k_scale, v_scale), (k8, v8))
 
 
-def prefill_attn_pos(q, k, v, pos, scale: float | None = None):
+def prefill_attn_pos(q, k, v, pos, scale: float | None = None, window: int | None = None):
     """Attention of query rows at positions of a KV cache: q [B, Hq, T, D] (any T >= 1), k / v [B, Hkv, S, D], ``pos``
     int64 [B, T] (need not be monotone).  Row (b, hq, t) attends keys ``0 .. n-1`` with ``n = clamp(pos[b, t] + 1, 0,
     S)``: what ``attn_fwd(q, k, v, causal=False, mask=position_mask(pos, S))[0]`` computes, bit for bit, without the
-    mask image and over the key tiles some row can see only.  ``n = 0`` gives a row of zeros, as there."""
+    mask image and over the key tiles some row can see only.  ``n = 0`` gives a row of zeros, as there.
+
+    ``window`` as ``decode_attn_pos`` takes it: the row attends keys ``max(0, n - window) .. n-1``, what ``attn_fwd``
+    computes under ``window_mask(pos, S, window)`` bit for bit, over the key tiles between the workgroup's lowest window
+    and its highest position only."""
     if not prefill_attn_pos_supported(q, k, v, pos):
         raise _refusal("prefill_attn_pos", q=q, k=k, v=v, pos=pos)
     q, k, v = _rows_in_place(q), _rows_in_place(k), _rows_in_place(v)
-    return _prefill_launch("lta_prefill_attn_pos", q, k, v, pos, scale)
+    return _prefill_launch("lta_prefill_attn_pos", q, k, v, pos, scale, window=window)
 
 
-def prefill_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None):
+def prefill_attn_kv8_pos(q, k8, v8, pos, scale: float | None = None, window: int | None = None):
     """``prefill_attn_pos`` over an unscaled e4m3 cache (uint8 bytes of ``float8_e4m3fn``): equals it over
     ``e4m3_values(k8, q.dtype)`` / ``e4m3_values(v8, q.dtype)`` bit for bit."""
     if not prefill_attn_kv8_pos_supported(q, k8, v8, pos):
         raise _refusal("prefill_attn_kv8_pos", q=q, k=k8, v=v8, pos=pos)
-    return _prefill_launch("lta_prefill_attn_kv8_pos", *_e4m3_in_place(q, k8, v8), pos, scale)
+    return _prefill_launch("lta_prefill_attn_kv8_pos", *_e4m3_in_place(q, k8, v8), pos, scale, window=window)
 
 
-def prefill_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None):
+def prefill_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None = None, window: int | None = None):
     """``prefill_attn_pos`` over the scaled e4m3 cache of ``ops/kv8.py``: equals it over ``dequantise_rows`` of the
     caches bit for bit; the scales are read in place."""
     if not prefill_attn_kv8s_pos_supported(q, k8, v8, k_scale, v_scale, pos):
         raise _refusal("prefill_attn_kv8s_pos", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos)
     return _prefill_launch("lta_prefill_attn_kv8s_pos", *_e4m3_in_place(q, k8, v8), pos, scale,
-                           scales=(k_scale, v_scale))
+                           scales=(k_scale, v_scale), window=window)
 
 
 def prefill_attn_paged_supported(q, k, v, pos, table, page_size, num_pages) -> bool:
@@ -733,7 +771,8 @@ def prefill_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, p
     return _paged_ok(q, k8, v8, pos, table, page_size, num_pages, torch.uint8, (k_scale, v_scale), max_queries=None)
 
 
-def prefill_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+def prefill_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scale: float | None = None,
+                       window: int | None = None):
     """``prefill_attn_pos`` over a paged cache: k / v pools ``[Hkv, R + 1, D]``, ``table`` int64 ``[B, max_pages]``.
     Row (b, hq, t) attends the keys ``j <= pos[b, t]`` (clamped to the capacity ``S = max_pages * page_size``) whose
     table entry lies in ``[0, num_pages)``, each read at pool row ``table[b, j // page_size] * page_size + j %
@@ -742,22 +781,23 @@ def prefill_attn_paged(q, k, v, pos, table, page_size: int, num_pages: int, scal
     if not prefill_attn_paged_supported(q, k, v, pos, table, page_size, num_pages):
         raise _refusal("prefill_attn_paged", q=q, k=k, v=v, pos=pos, table=table)
     return _prefill_launch("lta_prefill_attn_paged", _rows_in_place(q), k, v, pos, scale,
-                           pages=(table, page_size, num_pages))
+                           pages=(table, page_size, num_pages), window=window)
 
 
-def prefill_attn_kv8_paged(q, k8, v8, pos, table, page_size: int, num_pages: int, scale: float | None = None):
+def prefill_attn_kv8_paged(q, k8, v8, pos, table, page_size: int, num_pages: int, scale: float | None = None,
+                           window: int | None = None):
     """``prefill_attn_paged`` over unscaled e4m3 pools (uint8)."""
     if not prefill_attn_kv8_paged_supported(q, k8, v8, pos, table, page_size, num_pages):
         raise _refusal("prefill_attn_kv8_paged", q=q, k=k8, v=v8, pos=pos, table=table)
     return _prefill_launch("lta_prefill_attn_kv8_paged", _rows_in_place(q), k8, v8, pos, scale,
-                           pages=(table, page_size, num_pages))
+                           pages=(table, page_size, num_pages), window=window)
 
 
 def prefill_attn_kv8s_paged(q, k8, v8, k_scale, v_scale, pos, table, page_size: int, num_pages: int,
-                            scale: float | None = None):
+                            scale: float | None = None, window: int | None = None):
     """``prefill_attn_paged`` over the scaled e4m3 pools: bytes ``[Hkv, R + 1, D]`` and scale bytes ``[Hkv, R + 1, 1]``."""
     if not prefill_attn_kv8s_paged_supported(q, k8, v8, k_scale, v_scale, pos, table, page_size, num_pages):
         raise _refusal("prefill_attn_kv8s_paged", q=q, k=k8, v=v8, k_scale=k_scale, v_scale=v_scale, pos=pos,
                        table=table)
     return _prefill_launch("lta_prefill_attn_kv8s_paged", _rows_in_place(q), k8, v8, pos, scale,
-                           scales=(k_scale, v_scale), pages=(table, page_size, num_pages))
+                           scales=(k_scale, v_scale), pages=(table, page_size, num_pages), window=window)

@@ -92,8 +92,19 @@ struct PageMap {
 struct PagedPos : RowPos {
   PageMap pg;
 };
-template <bool POS, bool PAGED>
-using Selector = std::conditional_t<PAGED, PagedPos, std::conditional_t<POS, RowPos, NoPos>>;
+// Window mode (WIN, a position mode, static or paged): the row attends its last `window` >= 1 keys only, itself
+// included: key j iff p - window < j <= p (the Mistral / HF convention, ops/kv_rows.py window_mask), so the live range
+// is [lo, n) with lo = clamp(p + 1 - window, 0, n): max(0, n - window) for a position inside the cache, where
+// window >= S is the position mode.
+struct WinPos : RowPos {
+  int window;
+};
+struct WinPagedPos : PagedPos {
+  int window;
+};
+template <bool POS, bool PAGED, bool WIN = false>
+using Selector = std::conditional_t<WIN, std::conditional_t<PAGED, WinPagedPos, WinPos>,
+                                    std::conditional_t<PAGED, PagedPos, std::conditional_t<POS, RowPos, NoPos>>>;
 
 // KS (with KV = uint8_t): the cache is the scaled one.  The lane that owns key j loads that key's two scale
 // bytes (consecutive bytes across the lanes of a 64-key block) and forms 2^e as byte << 23; the score is
@@ -112,15 +123,24 @@ using Selector = std::conditional_t<PAGED, PagedPos, std::conditional_t<POS, Row
 // under an all-true mask bit for bit.  `mask`, `chunk` and `causal` are unused.  All three position kernels
 // round acc / l as the 16-bit kernel does (`normalised` with its scaled-cache form), so both e4m3 ones equal
 // the 16-bit one over the dequantised cache bit for bit, with the exclusions above (a zero result's sign included).
-template <typename T, typename KV, int D, bool WSPLIT, bool KS = false, bool POS = false, bool PAGED = false>
+//
+// WIN: the same split over the row's window, from its first 64-key block on: lo64 = lo & ~63, chunk_row =
+// round_up(ceil((n - lo64) / nsplit), 64), split s takes [lo64 + s * chunk_row, min(n, lo64 + (s + 1) * chunk_row)),
+// and a key is valid iff lo <= j < j_end.  A row at position 32767 under a window of 4096 then costs what a row at
+// 4095 costs.  On a paged cache the test stands before the table lookup: an entry below the window is never loaded
+// and may hold anything (PageTable.trim hands such pages back).  With lo = 0 all of this is the position mode's, bit
+// for bit; everything after `valid` is untouched.
+template <typename T, typename KV, int D, bool WSPLIT, bool KS = false, bool POS = false, bool PAGED = false,
+          bool WIN = false>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const T* __restrict__ q, const KV* __restrict__ k, const KV* __restrict__ v, const uint8_t* __restrict__ mask,
     T* __restrict__ o, float* __restrict__ ws_acc, float* __restrict__ ws_ml, int B, int Hq, int Hkv, int Tq, int S,
     int64_t qsb, int64_t qsh, int64_t qst, int64_t ksb, int64_t ksh, int64_t kss, int64_t vsb, int64_t vsh,
     int64_t vss, int64_t msb, int64_t msh, int64_t mst, int64_t mss, int chunk, int causal, float scale,
-    std::conditional_t<KS, KVScales, NoScales> sc, Selector<POS, PAGED> rp) {
+    std::conditional_t<KS, KVScales, NoScales> sc, Selector<POS, PAGED, WIN> rp) {
   static_assert(!KS || sizeof(KV) == 1, "scales belong to an e4m3 cache");
   static_assert(!PAGED || POS, "a paged cache is read by positions");
+  static_assert(!WIN || POS, "a window hangs on a row's position");
   constexpr int DPL = D / 64;          // output dims per lane after the final reduce-scatter
   constexpr bool kE4M3 = sizeof(KV) == 1;
   constexpr int NV = 16 / sizeof(KV);  // elements per 16-byte load
@@ -137,6 +157,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   int j_begin = split * chunk;
   int j_end = min(S, j_begin + chunk);
   if (causal) j_end = min(j_end, t + 1);
+  [[maybe_unused]] int lo = 0;  // WIN: the row's first live key
   if constexpr (POS) {
     // a wave owns one row: its position is one scalar load (the row index made uniform for the compiler)
     const int urow = __builtin_amdgcn_readfirstlane(row);
@@ -146,6 +167,13 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     const int chunk_row = ((n + nsplit - 1) / nsplit + 63) / 64 * 64;
     j_begin = split * chunk_row;
     j_end = min(n, j_begin + chunk_row);
+    if constexpr (WIN) {  // wave-uniform, as n is
+      lo = (int)min(max(p + 1 - (int64_t)rp.window, (int64_t)0), (int64_t)n);
+      const int lo64 = lo & ~63;
+      const int chunk_win = ((n - lo64 + nsplit - 1) / nsplit + 63) / 64 * 64;
+      j_begin = lo64 + split * chunk_win;
+      j_end = min(n, j_begin + chunk_win);
+    }
   }
 
   // scaled q row -> wave-private LDS (read back as broadcasts)
@@ -172,6 +200,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
   for (int j0 = j_begin + (WSPLIT ? w * 64 : 0); j0 < j_end; j0 += (WSPLIT ? kRowsPerBlock * 64 : 64)) {
     const int j = j0 + lane;
     bool valid = j < j_end;
+    if constexpr (WIN) valid = valid && j >= lo;
     if constexpr (!POS) {
       if (valid && mrow) valid = mrow[(int64_t)j * mss] != 0;
     }
@@ -321,20 +350,20 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
 }
 
-template <typename T, typename KV, int D, bool KS = false, bool POS = false, bool PAGED = false>
+template <typename T, typename KV, int D, bool KS = false, bool POS = false, bool PAGED = false, bool WIN = false>
 int launch(const void* q, const void* k, const void* v, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
            int Hq, int Hkv, int Tq, int S, const int64_t* st, int chunk, int nsplit, int causal, float scale,
            int wsplit, hipStream_t stream, std::conditional_t<KS, KVScales, NoScales> sc = {},
-           Selector<POS, PAGED> rp = {}) {
+           Selector<POS, PAGED, WIN> rp = {}) {
   const int rows = B * Tq * Hq;
   if (wsplit) {
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS, POS, PAGED>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS, POS, PAGED, WIN>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
                        (const KV*)k, (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
                        Tq, S, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11],
                        st[12], chunk, causal, scale, sc, rp);
   } else {
     dim3 grid((rows + kRowsPerBlock - 1) / kRowsPerBlock, nsplit);
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS, POS, PAGED>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
+    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS, POS, PAGED, WIN>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
                        (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
                        st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12],
                        chunk, causal, scale, sc, rp);
@@ -346,14 +375,14 @@ int launch(const void* q, const void* k, const void* v, const void* mask, void* 
 }
 
 // `launch` for q / o of `dtype` and head dim D; KV = void: the cache holds q's type.  `a`: launch's arguments.
-template <typename KV, bool KS = false, bool POS = false, bool PAGED = false, typename... A>
+template <typename KV, bool KS = false, bool POS = false, bool PAGED = false, bool WIN = false, typename... A>
 int dispatch(int dtype, int D, A... a) {
   using B16 = __hip_bfloat16;
   constexpr bool kSame = std::is_void_v<KV>;
-  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, POS, PAGED>(a...);
-  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, POS, PAGED>(a...);
-  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, POS, PAGED>(a...);
-  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, POS, PAGED>(a...);
+  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, POS, PAGED, WIN>(a...);
+  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, POS, PAGED, WIN>(a...);
+  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, POS, PAGED, WIN>(a...);
+  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, POS, PAGED, WIN>(a...);
   return (int)hipErrorInvalidValue;
 }
 
@@ -374,11 +403,12 @@ bool e4m3_cache_ok(const void* k, const void* v, const int64_t* strides) {
 // [B, Tq] (strides b,t; see RowPos).  KV = void: the cache holds q's type; uint8_t: e4m3.
 // PAGED: k / v (and the scales) are pools, their b strides 0 and S the logical capacity, a multiple of the page;
 // `table` int64 [B, S >> lg_page] with its strides b,p last in `strides`; see PageMap.
-template <typename KV, bool KS, bool POS, bool PAGED = false>
+// WIN: `window` >= 1 keys per row; anything less is refused and launches nothing.
+template <typename KV, bool KS, bool POS, bool PAGED = false, bool WIN = false>
 int decode_entry(int dtype, const void* q, const void* k, const void* v, const void* k_scale, const void* v_scale,
                  const void* sel, void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
                  const int64_t* strides, int chunk, int nsplit, int causal, float scale, int wsplit, void* stream,
-                 const void* table = nullptr, int lg_page = 0, int num_pages = 0) {
+                 const void* table = nullptr, int lg_page = 0, int num_pages = 0, int window = 0) {
   constexpr int kSel = POS ? 2 : 4;  // strides of the selector; the scales' follow them
   if (!sizes_ok(Hq, Hkv, POS ? 64 : chunk, nsplit)) return (int)hipErrorInvalidValue;  // POS: no chunk to check
   if (nsplit > 1 && (ws_acc == nullptr || ws_ml == nullptr)) return (int)hipErrorInvalidValue;
@@ -392,7 +422,11 @@ int decode_entry(int dtype, const void* q, const void* k, const void* v, const v
     const int64_t* ss = strides + 9 + kSel;
     sc = KVScales{(const uint8_t*)k_scale, (const uint8_t*)v_scale, ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]};
   }
-  Selector<POS, PAGED> rp{};
+  Selector<POS, PAGED, WIN> rp{};
+  if constexpr (WIN) {
+    if (window < 1) return (int)hipErrorInvalidValue;
+    rp.window = window;
+  }
   if constexpr (POS) {
     if (sel == nullptr || S < 0) return (int)hipErrorInvalidValue;
     rp.pos = (const int64_t*)sel;
@@ -406,7 +440,7 @@ int decode_entry(int dtype, const void* q, const void* k, const void* v, const v
     const int64_t* ts = strides + 9 + kSel + (KS ? 6 : 0);
     rp.pg = PageMap{(const int64_t*)table, ts[0], ts[1], lg_page, num_pages};
   }
-  return dispatch<KV, KS, POS, PAGED>(dtype, D, q, k, v, POS ? (const void*)nullptr : sel, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
+  return dispatch<KV, KS, POS, PAGED, WIN>(dtype, D, q, k, v, POS ? (const void*)nullptr : sel, o, ws_acc, ws_ml, B, Hq, Hkv, Tq, S,
                                (const int64_t*)st, chunk, nsplit, causal, scale, wsplit, (hipStream_t)stream, sc, rp);
 }
 
@@ -495,4 +529,61 @@ LTA_EXPORT int lta_decode_attn_kv8s_paged(int dtype, const void* q, const void* 
   return lta::decode_entry<uint8_t, true, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, ws_acc, ws_ml, B, Hq,
                                                       Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit, stream,
                                                       table, lg_page, num_pages);
+}
+
+// The window entries: the six position / paged entries with one trailing `window` (keys per row, >= 1; see WinPos).
+// window < 1 returns hipErrorInvalidValue and launches nothing.
+LTA_EXPORT int lta_decode_attn_pos_win(int dtype, const void* q, const void* k, const void* v, const void* pos, void* o,
+                                       void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                       const int64_t* strides, int nsplit, float scale, int wsplit, void* stream,
+                                       int window) {
+  return lta::decode_entry<void, false, true, false, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B, Hq,
+                                                           Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit, stream,
+                                                           nullptr, 0, 0, window);
+}
+
+LTA_EXPORT int lta_decode_attn_kv8_pos_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                           void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S,
+                                           int D, const int64_t* strides, int nsplit, float scale, int wsplit,
+                                           void* stream, int window) {
+  return lta::decode_entry<uint8_t, false, true, false, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B,
+                                                              Hq, Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit,
+                                                              stream, nullptr, 0, 0, window);
+}
+
+LTA_EXPORT int lta_decode_attn_kv8s_pos_win(int dtype, const void* q, const void* k, const void* v, const void* k_scale,
+                                            const void* v_scale, const void* pos, void* o, void* ws_acc, void* ws_ml,
+                                            int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
+                                            int nsplit, float scale, int wsplit, void* stream, int window) {
+  return lta::decode_entry<uint8_t, true, true, false, true>(dtype, q, k, v, k_scale, v_scale, pos, o, ws_acc, ws_ml, B,
+                                                             Hq, Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit,
+                                                             stream, nullptr, 0, 0, window);
+}
+
+LTA_EXPORT int lta_decode_attn_paged_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                         void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S,
+                                         int D, const int64_t* strides, int nsplit, float scale, int wsplit,
+                                         const void* table, int lg_page, int num_pages, void* stream, int window) {
+  return lta::decode_entry<void, false, true, true, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B, Hq,
+                                                          Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit, stream,
+                                                          table, lg_page, num_pages, window);
+}
+
+LTA_EXPORT int lta_decode_attn_kv8_paged_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                             void* o, void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S,
+                                             int D, const int64_t* strides, int nsplit, float scale, int wsplit,
+                                             const void* table, int lg_page, int num_pages, void* stream, int window) {
+  return lta::decode_entry<uint8_t, false, true, true, true>(dtype, q, k, v, nullptr, nullptr, pos, o, ws_acc, ws_ml, B,
+                                                             Hq, Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit,
+                                                             stream, table, lg_page, num_pages, window);
+}
+
+LTA_EXPORT int lta_decode_attn_kv8s_paged_win(int dtype, const void* q, const void* k, const void* v,
+                                              const void* k_scale, const void* v_scale, const void* pos, void* o,
+                                              void* ws_acc, void* ws_ml, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                              const int64_t* strides, int nsplit, float scale, int wsplit,
+                                              const void* table, int lg_page, int num_pages, void* stream, int window) {
+  return lta::decode_entry<uint8_t, true, true, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, ws_acc, ws_ml, B,
+                                                            Hq, Hkv, Tq, S, D, strides, 0, nsplit, 0, scale, wsplit,
+                                                            stream, table, lg_page, num_pages, window);
 }

@@ -19,6 +19,15 @@
 //  * e4m3 staging: a thread loads 16 bytes (16 elements), unpacks them with v_cvt_pk_f32_fp8, with KS multiplies by
 //    the row's 2^e (scale byte << 23), rounds to T (exact: ops/kv8.py) and writes 32 bytes to LDS.  The LDS tile is
 //    then the dequantised cache's bit for bit and everything after staging is the 16-bit instantiation's code.
+//  * WIN (a sliding window of `window` >= 1 keys per row, itself included: key j iff p - window < j <= p, the Mistral /
+//    HF convention): every lane also has its row's first live key lo = clamp(p + 1 - window, 0, n), which is
+//    max(0, n - window) for a position inside the cache.  The tile loop starts at
+//    floor(lo_min / 64) with lo_min the workgroup's smallest lo over rows with n > 0 (rows with n = 0, those >= Tq of the
+//    last query tile among them, take no part); a key below lo_min is dead like one at or past nmax (zeros staged,
+//    nothing loaded, on a paged cache no table lookup: PageTable.trim may have taken the page back); the score stage
+//    sets -inf for j < lo of its row, and a tile needs no per-key select only if it lies in [lo_high, n_low) with
+//    lo_high the wave's largest lo.  A skipped leading tile would have left m = -inf, l = 0 and O = 0, so the result is
+//    still the masked v1 forward's bit for bit.
 // No split over keys: 17 .. 128 rows at batch 1 fill Hq workgroups, as the masked launch this replaces does.
 #include <type_traits>
 
@@ -53,6 +62,17 @@ struct PageMap {
   int lg_page, num_pages;
 };
 struct NoPages {};
+// Sliding window (WIN): `window` >= 1 keys per row, carried behind the page map so that the kernels without a window
+// keep their argument lists.
+struct WinPageMap : PageMap {
+  int window;
+};
+struct WinNoPages {
+  int window;
+};
+template <bool PAGED, bool WIN>
+using Pages = std::conditional_t<WIN, std::conditional_t<PAGED, WinPageMap, WinNoPages>,
+                                 std::conditional_t<PAGED, PageMap, NoPages>>;
 
 // Element strides (batch, head, token / key row) of Q, K, V and O; head dim contiguous.
 struct Strides {
@@ -83,11 +103,11 @@ __device__ __forceinline__ void unpack16_e4m3(const uint4& x, float (&f)[16]) {
   }
 }
 
-template <typename T, typename KV, int D, bool KS, bool PAGED>
+template <typename T, typename KV, int D, bool KS, bool PAGED, bool WIN = false>
 __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
     const T* __restrict__ Q, const KV* __restrict__ K, const KV* __restrict__ V, T* __restrict__ O, int Hq, int Hkv,
     int Tq, int S, float scale_log2, Strides sx, RowPos rp, std::conditional_t<KS, KVScales, NoScales> sc,
-    std::conditional_t<PAGED, PageMap, NoPages> pg) {
+    Pages<PAGED, WIN> pg) {
   static_assert(!KS || sizeof(KV) == 1, "scales belong to an e4m3 cache");
   constexpr bool kE4M3 = sizeof(KV) == 1;
   using C = Cfg<D, sizeof(KV)>;
@@ -95,6 +115,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
   __shared__ __attribute__((aligned(16))) short smem[kBN * C::KSTR + kBN * C::VSTR];
   __shared__ __attribute__((aligned(16))) uint8_t dead_lds[kBN];  // PAGED: 1 for a key of the tile that is not staged
   __shared__ int wave_n[kThreads / 64];
+  __shared__ int wave_first[WIN ? kThreads / 64 : 1];  // WIN: every wave's smallest lo over its rows with n > 0
   short* Ks = smem;
   short* Vs = smem + kBN * C::KSTR;
   const __attribute__((address_space(3))) short* Vs3 = (const __attribute__((address_space(3))) short*)Vs;
@@ -123,9 +144,11 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
 
   // this row's key count, the wave's smallest (below it no key of a tile needs the select) and the workgroup's largest
   int n = 0;
+  [[maybe_unused]] int lo = 0;  // WIN: this row's first live key
   if (qi < Tq) {
     const int64_t p = rp.pos[b * rp.sb + (int64_t)qi * rp.st];
     n = (int)min(max(p + 1, (int64_t)0), (int64_t)S);
+    if constexpr (WIN) lo = (int)min(max(p + 1 - (int64_t)pg.window, (int64_t)0), (int64_t)n);
   }
   int nmx = n, nmn = n;
 #pragma unroll
@@ -135,9 +158,27 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
   }
   const int n_low = __builtin_amdgcn_readfirstlane(nmn);
   if (lane == 0) wave_n[wave] = nmx;
+  // WIN: the wave's largest lo (a tile below it needs the select) and its smallest over the rows that attend anything
+  [[maybe_unused]] int lo_high = 0, lo_min = 0;
+  if constexpr (WIN) {
+    int lmx = lo, lmn = n > 0 ? lo : INT32_MAX;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {
+      lmx = max(lmx, __shfl_xor(lmx, o, 64));
+      lmn = min(lmn, __shfl_xor(lmn, o, 64));
+    }
+    lo_high = __builtin_amdgcn_readfirstlane(lmx);
+    if (lane == 0) wave_first[wave] = lmn;
+  }
   __syncthreads();
   const int nmax = __builtin_amdgcn_readfirstlane(max(max(wave_n[0], wave_n[1]), max(wave_n[2], wave_n[3])));
   const int n_tiles = (nmax + kBN - 1) / kBN;  // workgroup-uniform: the loop holds barriers
+  int t_first = 0;
+  if constexpr (WIN) {
+    // INT32_MAX when no row attends: no tile either
+    lo_min = __builtin_amdgcn_readfirstlane(min(min(wave_first[0], wave_first[1]), min(wave_first[2], wave_first[3])));
+    t_first = lo_min / kBN;
+  }
 
   // Q fragments (B operand of S^T = K Q^T): Q[qi][16s + 8h .. +7]
   F qf[C::KSTEPS];
@@ -166,7 +207,9 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
       for (int c = 0; c < C::LOADS; ++c) {
         const int key = t * kBN + (c * kThreads + tid) / C::CH;
         int pr = -1;
-        if (key < nmax) {  // nmax <= S = (table entries per sequence) << lg_page
+        bool inside = key < nmax;  // nmax <= S = (table entries per sequence) << lg_page
+        if constexpr (WIN) inside = inside && key >= lo_min;  // below every row's window: no table lookup
+        if (inside) {
           const int64_t pid = pg.table[b * pg.sb + (int64_t)(key >> pg.lg_page) * pg.sp];
           if (pid >= 0 && pid < pg.num_pages) pr = (int)(pid << pg.lg_page) + (key & ((1 << pg.lg_page) - 1));
         }
@@ -182,6 +225,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
       const int row = id / C::CH, ch = id % C::CH;
       int64_t kr = t * kBN + row;  // the key's row in its cache
       bool live = kr < nmax;
+      if constexpr (WIN) live = live && kr >= lo_min;
       if constexpr (PAGED) {
         kr = prow[c];
         live = kr >= 0;
@@ -239,12 +283,12 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
     }
   };
 
-  if (n_tiles > 0) {
-    tload(0);
-    gload(0);
-    if (n_tiles > 1) tload(1);
+  if (t_first < n_tiles) {
+    tload(t_first);
+    gload(t_first);
+    if (t_first + 1 < n_tiles) tload(t_first + 1);
   }
-  for (int t = 0; t < n_tiles; ++t) {
+  for (int t = t_first; t < n_tiles; ++t) {
     __syncthreads();  // previous tile fully consumed
     lstore();
     __syncthreads();
@@ -270,7 +314,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
 
     // ---- scale, dead keys, online softmax (lane-local row = query qi): v1's arithmetic and order ----------
     const int kbase = t * kBN;
-    const bool need_mask = PAGED || kbase + kBN > n_low;  // wave-uniform
+    const bool need_mask = PAGED || kbase + kBN > n_low || (WIN && kbase < lo_high);  // wave-uniform
     [[maybe_unused]] uint32_t dead4[8];  // PAGED: the flags of this lane's keys, 4 consecutive keys per word
     if constexpr (PAGED) {
 #pragma unroll
@@ -288,6 +332,7 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
         if (need_mask) {
           const int key = kbase + kt * 32 + acc_row(i, h);
           bool dead = key >= n;
+          if constexpr (WIN) dead = dead || key < lo;
           if constexpr (PAGED) dead = dead || ((dead4[kt * 4 + (i >> 2)] >> (8 * (i & 3))) & 0xffu) != 0;
           v = dead ? -INFINITY : v;
         }
@@ -359,26 +404,26 @@ __global__ __launch_bounds__(kThreads, 2) void prefill_attn_kernel(
   }
 }
 
-template <typename T, typename KV, int D, bool KS, bool PAGED>
+template <typename T, typename KV, int D, bool KS, bool PAGED, bool WIN>
 int launch(const void* q, const void* k, const void* v, void* o, int B, int Hq, int Hkv, int Tq, int S, float scale,
            const Strides& sx, const RowPos& rp, std::conditional_t<KS, KVScales, NoScales> sc,
-           std::conditional_t<PAGED, PageMap, NoPages> pg, hipStream_t stream) {
+           Pages<PAGED, WIN> pg, hipStream_t stream) {
   const float sl2 = scale * 1.44269504088896340736f;
   dim3 grid(B * Hq, (Tq + kBM - 1) / kBM), block(kThreads);
-  hipLaunchKernelGGL((prefill_attn_kernel<T, KV, D, KS, PAGED>), grid, block, 0, stream, (const T*)q, (const KV*)k,
-                     (const KV*)v, (T*)o, Hq, Hkv, Tq, S, sl2, sx, rp, sc, pg);
+  hipLaunchKernelGGL((prefill_attn_kernel<T, KV, D, KS, PAGED, WIN>), grid, block, 0, stream, (const T*)q,
+                     (const KV*)k, (const KV*)v, (T*)o, Hq, Hkv, Tq, S, sl2, sx, rp, sc, pg);
   return (int)hipGetLastError();
 }
 
 // `launch` for q / o of `dtype` and head dim D; KV = void: the cache holds q's type.
-template <typename KV, bool KS, bool PAGED, typename... A>
+template <typename KV, bool KS, bool PAGED, bool WIN, typename... A>
 int dispatch(int dtype, int D, A... a) {
   using B16 = __hip_bfloat16;
   constexpr bool kSame = std::is_void_v<KV>;
-  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, PAGED>(a...);
-  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, PAGED>(a...);
-  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, PAGED>(a...);
-  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, PAGED>(a...);
+  if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, PAGED, WIN>(a...);
+  if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, PAGED, WIN>(a...);
+  if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, PAGED, WIN>(a...);
+  if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, PAGED, WIN>(a...);
   return (int)hipErrorInvalidValue;
 }
 
@@ -387,12 +432,13 @@ int dispatch(int dtype, int D, A... a) {
 //   q b,h,t | k b,h,s | v b,h,s | pos b,t | with KS: k scale b,h,s | v scale b,h,s (bytes) | with PAGED: table b,p
 // as decode_attention.hip decode_entry has them, and `o_strides` = O's b,h,t.  KV = void: the cache holds q's type;
 // uint8_t: e4m3.  PAGED: k / v (and the scales) are pools, their b strides 0 and S the logical capacity, a multiple
-// of the page; `table` int64 [B, S >> lg_page].  A refusal returns hipErrorInvalidValue and launches nothing.
-template <typename KV, bool KS, bool PAGED>
+// of the page; `table` int64 [B, S >> lg_page].  WIN: `window` >= 1 keys per row.  A refusal returns
+// hipErrorInvalidValue and launches nothing.
+template <typename KV, bool KS, bool PAGED, bool WIN = false>
 int prefill_entry(int dtype, const void* q, const void* k, const void* v, const void* k_scale, const void* v_scale,
                   const void* pos, void* o, int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
                   const int64_t* o_strides, float scale, void* stream, const void* table = nullptr, int lg_page = 0,
-                  int num_pages = 0) {
+                  int num_pages = 0, int window = 0) {
   constexpr bool kE4M3 = std::is_same_v<KV, uint8_t>;
   if (q == nullptr || k == nullptr || v == nullptr || o == nullptr || pos == nullptr || strides == nullptr ||
       o_strides == nullptr)
@@ -415,15 +461,20 @@ int prefill_entry(int dtype, const void* q, const void* k, const void* v, const 
     const int64_t* ss = strides + 11;
     sc = KVScales{(const uint8_t*)k_scale, (const uint8_t*)v_scale, ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]};
   }
-  std::conditional_t<PAGED, PageMap, NoPages> pg{};
+  Pages<PAGED, WIN> pg{};
+  if constexpr (WIN) {
+    if (window < 1) return (int)hipErrorInvalidValue;
+    pg.window = window;
+  }
   if constexpr (PAGED) {
     if (table == nullptr || lg_page < 4 || lg_page > 24 || num_pages <= 0 || num_pages > (INT32_MAX >> lg_page) ||
         S % (1 << lg_page))
       return (int)hipErrorInvalidValue;
     const int64_t* ts = strides + 11 + (KS ? 6 : 0);
-    pg = PageMap{(const int64_t*)table, ts[0], ts[1], lg_page, num_pages};
+    static_cast<PageMap&>(pg) = PageMap{(const int64_t*)table, ts[0], ts[1], lg_page, num_pages};
   }
-  return dispatch<KV, KS, PAGED>(dtype, D, q, k, v, o, B, Hq, Hkv, Tq, S, scale, sx, rp, sc, pg, (hipStream_t)stream);
+  return dispatch<KV, KS, PAGED, WIN>(dtype, D, q, k, v, o, B, Hq, Hkv, Tq, S, scale, sx, rp, sc, pg,
+                                      (hipStream_t)stream);
 }
 
 }  // namespace
@@ -478,4 +529,54 @@ LTA_EXPORT int lta_prefill_attn_kv8s_paged(int dtype, const void* q, const void*
                                            float scale, const void* table, int lg_page, int num_pages, void* stream) {
   return prefill_entry<uint8_t, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, B, Hq, Hkv, Tq, S, D, strides,
                                             o_strides, scale, stream, table, lg_page, num_pages);
+}
+
+// The window entries: the six entries above with one trailing `window` (keys per row, >= 1; see Window).
+// window < 1 returns hipErrorInvalidValue and launches nothing.
+LTA_EXPORT int lta_prefill_attn_pos_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                        void* o, int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
+                                        const int64_t* o_strides, float scale, void* stream, int window) {
+  return prefill_entry<void, false, false, true>(dtype, q, k, v, nullptr, nullptr, pos, o, B, Hq, Hkv, Tq, S, D, strides,
+                                                 o_strides, scale, stream, nullptr, 0, 0, window);
+}
+
+LTA_EXPORT int lta_prefill_attn_kv8_pos_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                            void* o, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                            const int64_t* strides, const int64_t* o_strides, float scale, void* stream,
+                                            int window) {
+  return prefill_entry<uint8_t, false, false, true>(dtype, q, k, v, nullptr, nullptr, pos, o, B, Hq, Hkv, Tq, S, D,
+                                                    strides, o_strides, scale, stream, nullptr, 0, 0, window);
+}
+
+LTA_EXPORT int lta_prefill_attn_kv8s_pos_win(int dtype, const void* q, const void* k, const void* v,
+                                             const void* k_scale, const void* v_scale, const void* pos, void* o, int B,
+                                             int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
+                                             const int64_t* o_strides, float scale, void* stream, int window) {
+  return prefill_entry<uint8_t, true, false, true>(dtype, q, k, v, k_scale, v_scale, pos, o, B, Hq, Hkv, Tq, S, D,
+                                                   strides, o_strides, scale, stream, nullptr, 0, 0, window);
+}
+
+LTA_EXPORT int lta_prefill_attn_paged_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                          void* o, int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
+                                          const int64_t* o_strides, float scale, const void* table, int lg_page,
+                                          int num_pages, void* stream, int window) {
+  return prefill_entry<void, false, true, true>(dtype, q, k, v, nullptr, nullptr, pos, o, B, Hq, Hkv, Tq, S, D, strides,
+                                                o_strides, scale, stream, table, lg_page, num_pages, window);
+}
+
+LTA_EXPORT int lta_prefill_attn_kv8_paged_win(int dtype, const void* q, const void* k, const void* v, const void* pos,
+                                              void* o, int B, int Hq, int Hkv, int Tq, int S, int D,
+                                              const int64_t* strides, const int64_t* o_strides, float scale,
+                                              const void* table, int lg_page, int num_pages, void* stream, int window) {
+  return prefill_entry<uint8_t, false, true, true>(dtype, q, k, v, nullptr, nullptr, pos, o, B, Hq, Hkv, Tq, S, D,
+                                                   strides, o_strides, scale, stream, table, lg_page, num_pages, window);
+}
+
+LTA_EXPORT int lta_prefill_attn_kv8s_paged_win(int dtype, const void* q, const void* k, const void* v,
+                                               const void* k_scale, const void* v_scale, const void* pos, void* o,
+                                               int B, int Hq, int Hkv, int Tq, int S, int D, const int64_t* strides,
+                                               const int64_t* o_strides, float scale, const void* table, int lg_page,
+                                               int num_pages, void* stream, int window) {
+  return prefill_entry<uint8_t, true, true, true>(dtype, q, k, v, k_scale, v_scale, pos, o, B, Hq, Hkv, Tq, S, D, strides,
+                                                  o_strides, scale, stream, table, lg_page, num_pages, window);
 }

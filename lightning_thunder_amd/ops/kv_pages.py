@@ -72,6 +72,15 @@ def paged_mask(pos: torch.Tensor, table: torch.Tensor, page_size: int, num_pages
     return (j <= pos[:, None, :, None]) & live[:, None, None, :]
 
 
+def paged_window_mask(pos: torch.Tensor, table: torch.Tensor, page_size: int, num_pages: Optional[int],
+                      window: int) -> torch.Tensor:
+    """bool ``[B, 1, T, S]``: ``paged_mask`` under a sliding window, and-ed with ``j > pos[b, t] - window`` (``window``
+    keys, the token's own included: the Mistral / HF convention).  A page wholly below every row's window may hold
+    any table entry: its keys are hidden either way, which is what lets ``PageTable.trim`` take it back."""
+    j = torch.arange(table.shape[1] * page_size, device=pos.device)
+    return paged_mask(pos, table, page_size, num_pages) & (j > pos[:, None, :, None] - window)
+
+
 def write_slots(pool: torch.Tensor, slots: torch.Tensor, src: torch.Tensor) -> torch.Tensor:
     """``pool[:, slots[b, t], :] = src[b, :, t, :]`` in place (pool ``[H, R + 1, D]``, src ``[B, H, T, D]``, slots
     int64 ``[B, T]``): the ``[H, B * T, D]`` relayout, then one ``index_copy_`` along the rows.  Returns ``pool``."""
@@ -111,12 +120,27 @@ def _kv_paged_mask_fake(pos, table, page_size, num_pages):
     return pos.new_empty((B, 1, T, table.shape[1] * page_size), dtype=torch.bool)
 
 
+@torch.library.custom_op("lta::kv_paged_window_mask", mutates_args=())
+def kv_paged_window_mask(pos: torch.Tensor, table: torch.Tensor, page_size: int, num_pages: int,
+                         window: int) -> torch.Tensor:
+    return paged_window_mask(pos, table, page_size, num_pages, window)
+
+
+@kv_paged_window_mask.register_fake
+def _kv_paged_window_mask_fake(pos, table, page_size, num_pages, window):
+    B, T = pos.shape
+    return pos.new_empty((B, 1, T, table.shape[1] * page_size), dtype=torch.bool)
+
+
 class PageTable:
     """The host-side allocator of a paged cache; it owns the device block table ``table`` (int64
     ``[batch_size, max_pages]``, ``-1`` = no page).
 
     The allocator works from host-side lengths only and synchronises nothing.  The device table is updated in
-    place, at a fixed address, so a captured decode step keeps replaying while sequences grow."""
+    place, at a fixed address, so a captured decode step keeps replaying while sequences grow.
+
+    Under a sliding window a sequence gives its lowest pages back (``trim``): it then holds the table indices
+    ``first .. end - 1``, the entries below ``first`` are ``-1`` again and stay so until ``release``."""
 
     def __init__(self, batch_size: int, max_pages: int, page_size: int, num_pages: int, device=None):
         self.page_size = check_page_size(page_size)
@@ -126,7 +150,9 @@ class PageTable:
         self.batch_size, self.max_pages, self.num_pages = batch_size, max_pages, num_pages
         self.table = torch.full((batch_size, max_pages), -1, dtype=torch.int64, device=device)
         self._host = torch.full((batch_size, max_pages), -1, dtype=torch.int64)
-        self._held = [0] * batch_size  # pages of every sequence
+        self._held = [0] * batch_size  # every sequence's table index past its last page
+        self._first = [0] * batch_size  # and that of its first page: the indices below it were trimmed
+        self.peak_pages_in_use = 0  # the most pages out at once since the last reset()
         self._free = list(range(num_pages))  # a heap: the lowest free page goes out first
 
     @property
@@ -144,11 +170,12 @@ class PageTable:
         return self.num_pages - len(self._free)
 
     def pages_of(self, b: int) -> list[int]:
-        return self._host[b, :self._held[b]].tolist()
+        return self._host[b, self._first[b]:self._held[b]].tolist()
 
     def reserve(self, lengths: Sequence[int]) -> None:
-        """Gives every sequence ``ceil(lengths[b] / page_size)`` pages, lowest free page first.  A page a sequence
-        already has never moves, and a sequence keeps pages beyond its length.  ``ValueError`` for a length beyond
+        """Gives every sequence pages up to table index ``ceil(lengths[b] / page_size)``, lowest free page first.  A
+        page a sequence already has never moves, a sequence keeps pages beyond its length, and a table index that
+        ``trim`` emptied gets no page again.  ``ValueError`` for a length beyond
         ``max_pages`` pages, ``RuntimeError`` when the pool has too few free pages; neither changes anything."""
         lengths = [int(n) for n in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
         if len(lengths) != self.batch_size:
@@ -167,13 +194,32 @@ class PageTable:
             for i in range(self._held[b], n):
                 self._host[b, i] = heapq.heappop(self._free)
             self._held[b] = n
+        self.peak_pages_in_use = max(self.peak_pages_in_use, self.pages_in_use)
         self.table.copy_(self._host)
+
+    def trim(self, first_live: Sequence[int]) -> None:
+        """The pages of sequence b that lie wholly below position ``first_live[b]`` go back to the free list and their
+        table entries become ``-1``: what a sliding window leaves behind.  A page that holds ``first_live[b]`` stays.
+        Host-side only, no synchronisation; the device table is updated in place when anything changed."""
+        first_live = [int(n) for n in (first_live.tolist() if isinstance(first_live, torch.Tensor) else first_live)]
+        if len(first_live) != self.batch_size:
+            raise ValueError(f"PageTable.trim: {len(first_live)} positions for a batch of {self.batch_size}")
+        changed = False
+        for b, n in enumerate(first_live):
+            upto = min(max(n, 0) // self.page_size, self._held[b])
+            for i in range(self._first[b], upto):
+                heapq.heappush(self._free, int(self._host[b, i]))
+                self._host[b, i] = -1
+                changed = True
+            self._first[b] = max(self._first[b], upto)
+        if changed:
+            self.table.copy_(self._host)
 
     def release(self, b: int) -> None:
         """The pages of sequence ``b`` go back to the free list; its table row becomes ``-1``."""
         for p in self.pages_of(b):
             heapq.heappush(self._free, p)
-        self._held[b] = 0
+        self._held[b] = self._first[b] = 0
         self._host[b] = -1
         self.table.copy_(self._host)
 
@@ -181,3 +227,4 @@ class PageTable:
         for b in range(self.batch_size):
             if self._held[b]:
                 self.release(b)
+        self.peak_pages_in_use = 0
