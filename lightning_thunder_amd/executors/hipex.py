@@ -2658,6 +2658,13 @@ def _broadcastable(shape, target) -> bool:
     return True
 
 
+def _decode_head_dim(D) -> bool:
+    """64 / 128, and 256 (the wide-row kernel) unless LTA_DECODE_D256=0."""
+    from ..ops.attention import DECODE_WIDE_HEAD_DIM, decode_wide_off
+
+    return D in (64, 128) or (D == DECODE_WIDE_HEAD_DIM and not decode_wide_off())
+
+
 def _is_decode_shape(query, key, attn_mask) -> bool:
     from ..ops.attention import DECODE_MAX_QUERIES
 
@@ -2674,7 +2681,7 @@ def _is_decode(query, key, attn_mask) -> bool:
     if attn_mask is None or not isinstance(attn_mask, TensorProxy) or attn_mask.dtype != torch.bool:
         return False
     B, Hq, T, D = query.shape
-    if D not in (64, 128):  # the decode kernel's head dims (others take the padded flash path)
+    if not _decode_head_dim(D):  # the decode kernels' head dims (others take the padded flash path)
         return False
     return T <= DECODE_MAX_QUERIES and _broadcastable(tuple(attn_mask.shape), (B, Hq, T, key.shape[2]))
 
@@ -2708,7 +2715,7 @@ def _sdpa_checker(query, key, value, attn_mask=None, dropout_p=0.0, is_causal=Fa
         return False
     if D > PLAIN_ONLY_HEAD_DIM and (attn_mask is not None or p > 0.0):
         return False
-    if D not in (64, 128) and _is_decode_shape(query, key, attn_mask):
+    if not _decode_head_dim(D) and _is_decode_shape(query, key, attn_mask):
         return False  # decode steps at head dims without a decode kernel stay on ATen (padding buys nothing there)
     if key.shape[1] != value.shape[1] or query.shape[1] % key.shape[1] != 0:
         return False

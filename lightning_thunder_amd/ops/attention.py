@@ -392,6 +392,18 @@ for _entry, _scale_ptrs in (("lta_decode_attn", 0), ("lta_decode_attn_kv8", 0), 
     register_signature(_entry + "_paged_win", [*_head, c_int, c_float, c_int, c_void_p, c_int, c_int, c_void_p, c_int])
 
 DECODE_MAX_QUERIES = 16
+DECODE_WIDE_HEAD_DIM = 256  # the decode kernels' third head dim (csrc/decode_attention_wide.h); the prefill kernel has none
+
+
+def decode_wide_off() -> bool:
+    """LTA_DECODE_D256=0 keeps decode steps at head dim 256 off the decode kernels: the compiler leaves their
+    attention to ATen, as before the wide-row kernel (A/B against it).  The wrappers here take 256 either way."""
+    return os.environ.get("LTA_DECODE_D256", "1") == "0"
+
+
+def _head_dim_ok(D: int, max_queries) -> bool:
+    """64 / 128 for every kernel that reads a KV cache, 256 as well for the decode kernels (``max_queries`` set)."""
+    return D in (64, 128) or (max_queries is not None and D == DECODE_WIDE_HEAD_DIM)
 
 
 def decode_launch_shape(rows: int, S: int):
@@ -477,10 +489,10 @@ def _refusal(fn: str, **operands) -> ValueError:
 
 
 def _cache_operands_ok(q, k, v, cache_dtype, max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
-    """The shape rule of every kernel that checks its operands: 16-bit q [B, Hq, T, D] with D 64 / 128 and at most
-    ``max_queries`` rows (the decode kernels' DECODE_MAX_QUERIES; None for the prefill kernel: any number), k / v
-    [B, Hkv, S, D] of ``cache_dtype`` with Hkv dividing Hq."""
-    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
+    """The shape rule of every kernel that checks its operands: 16-bit q [B, Hq, T, D] with D 64 / 128 (the decode
+    kernels: 256 too) and at most ``max_queries`` rows (the decode kernels' DECODE_MAX_QUERIES; None for the prefill
+    kernel: any number), k / v [B, Hkv, S, D] of ``cache_dtype`` with Hkv dividing Hq."""
+    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and _head_dim_ok(q.shape[-1], max_queries)
             and (max_queries is None or q.shape[2] <= max_queries) and k.dtype == cache_dtype and v.dtype == cache_dtype
             and k.dim() == 4 and k.shape == v.shape and k.shape[-1] == q.shape[-1] and k.shape[0] == q.shape[0]
             and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0)
@@ -497,7 +509,7 @@ def decode_attn(q, k, v, mask=None, causal: bool = False, scale: float | None = 
 
 
 def decode_attn_kv8_supported(q, k8, v8) -> bool:
-    """What the e4m3-cache decode kernel takes: 16-bit q of head dim 64 / 128, uint8 k / v."""
+    """What the e4m3-cache decode kernel takes: 16-bit q of head dim 64 / 128 / 256, uint8 k / v."""
     return _cache_operands_ok(q, k8, v8, torch.uint8)
 
 
@@ -545,7 +557,7 @@ def _pos_ok(q, k, pos, max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
 
 
 def decode_attn_pos_supported(q, k, v, pos) -> bool:
-    """What the 16-bit position kernel takes: bf16 / fp16 q, k, v of one dtype and head dim 64 / 128, GQA
+    """What the 16-bit position kernel takes: bf16 / fp16 q, k, v of one dtype and head dim 64 / 128 / 256, GQA
     head counts, int64 ``pos`` [B, T] with T <= 16."""
     return _pos_ok(q, k, pos) and _cache_operands_ok(q, k, v, q.dtype)
 
@@ -596,15 +608,15 @@ def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None =
 # ------------------------------------------------------------------------------------------------
 def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=(),
               max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
-    """16-bit q [B, Hq, T, D] with D 64 / 128 and at most ``max_queries`` rows (None: any number); pools k / v
-    [Hkv, rows, D] of ``cache_dtype`` read in place (head dim contiguous, 16-byte aligned rows and heads) with Hkv dividing Hq and
+    """16-bit q [B, Hq, T, D] with D 64 / 128 (the decode kernels: 256 too) and at most ``max_queries`` rows (None: any
+    number); pools k / v [Hkv, rows, D] of ``cache_dtype`` read in place (head dim contiguous, 16-byte aligned rows and heads) with Hkv dividing Hq and
     ``rows >= num_pages * page_size``; scale pools uint8 [Hkv, rows, 1]; int64 ``pos`` [B, T] and ``table``
     [B, max_pages >= 1] on q's device; ``page_size`` a power of two >= 16 and ``num_pages`` >= 1, both ints."""
     if not all(isinstance(n, int) and not isinstance(n, bool) for n in (page_size, num_pages)):
         return False
     if page_size < 16 or page_size & (page_size - 1) or num_pages < 1 or num_pages * page_size >= 2 ** 31:
         return False
-    if not (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and q.shape[-1] in (64, 128)
+    if not (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and _head_dim_ok(q.shape[-1], max_queries)
             and 0 < q.shape[2] and (max_queries is None or q.shape[2] <= max_queries)):
         return False
     unit = 16 // k.element_size()  # elements per 16 bytes

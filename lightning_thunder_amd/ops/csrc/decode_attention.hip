@@ -350,6 +350,24 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(const float* __
   for (int i = 0; i < DPL; ++i) orow[i] = normalised<T, KV, KS>(acc[i], inv);
 }
 
+}  // namespace
+}  // namespace lta
+
+#include "decode_attention_wide.h"
+
+namespace lta {
+namespace {
+
+// The kernel of head dim D: the wide-row one (decode_attention_wide.h) at 256, decode_attn_kernel below it.  Both
+// take the same arguments on the same grid.
+template <typename T, typename KV, int D, bool WSPLIT, bool KS, bool POS, bool PAGED, bool WIN>
+constexpr auto decode_kernel_of() {
+  if constexpr (D == 256)
+    return &decode_attn_wide_kernel<T, KV, D, WSPLIT, KS, POS, PAGED, WIN>;
+  else
+    return &decode_attn_kernel<T, KV, D, WSPLIT, KS, POS, PAGED, WIN>;
+}
+
 template <typename T, typename KV, int D, bool KS = false, bool POS = false, bool PAGED = false, bool WIN = false>
 int launch(const void* q, const void* k, const void* v, const void* mask, void* o, void* ws_acc, void* ws_ml, int B,
            int Hq, int Hkv, int Tq, int S, const int64_t* st, int chunk, int nsplit, int causal, float scale,
@@ -357,13 +375,13 @@ int launch(const void* q, const void* k, const void* v, const void* mask, void* 
            Selector<POS, PAGED, WIN> rp = {}) {
   const int rows = B * Tq * Hq;
   if (wsplit) {
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, true, KS, POS, PAGED, WIN>), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
+    hipLaunchKernelGGL((decode_kernel_of<T, KV, D, true, KS, POS, PAGED, WIN>()), dim3(rows, nsplit), dim3(256), 0, stream, (const T*)q,
                        (const KV*)k, (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv,
                        Tq, S, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11],
                        st[12], chunk, causal, scale, sc, rp);
   } else {
     dim3 grid((rows + kRowsPerBlock - 1) / kRowsPerBlock, nsplit);
-    hipLaunchKernelGGL((decode_attn_kernel<T, KV, D, false, KS, POS, PAGED, WIN>), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
+    hipLaunchKernelGGL((decode_kernel_of<T, KV, D, false, KS, POS, PAGED, WIN>()), grid, dim3(256), 0, stream, (const T*)q, (const KV*)k,
                        (const KV*)v, (const uint8_t*)mask, (T*)o, (float*)ws_acc, (float*)ws_ml, B, Hq, Hkv, Tq, S,
                        st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], st[9], st[10], st[11], st[12],
                        chunk, causal, scale, sc, rp);
@@ -383,6 +401,8 @@ int dispatch(int dtype, int D, A... a) {
   if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, POS, PAGED, WIN>(a...);
   if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, POS, PAGED, WIN>(a...);
   if (dtype == kF16 && D == 128) return launch<__half, std::conditional_t<kSame, __half, KV>, 128, KS, POS, PAGED, WIN>(a...);
+  if (dtype == kBF16 && D == 256) return launch<B16, std::conditional_t<kSame, B16, KV>, 256, KS, POS, PAGED, WIN>(a...);
+  if (dtype == kF16 && D == 256) return launch<__half, std::conditional_t<kSame, __half, KV>, 256, KS, POS, PAGED, WIN>(a...);
   return (int)hipErrorInvalidValue;
 }
 
