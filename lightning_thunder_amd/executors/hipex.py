@@ -1498,8 +1498,17 @@ def _kv_prefill_fusion_off() -> bool:
     return os.environ.get("LTA_KV_PREFILL_FUSION", "1") == "0"
 
 
+def _prefill_head_dim(q) -> bool:
+    """64 / 128, and 256 (csrc/prefill_attention_d256.hip) past the decode kernels' rows unless LTA_PREFILL_D256=0."""
+    from ..ops.attention import DECODE_MAX_QUERIES, DECODE_WIDE_HEAD_DIM, prefill_wide_off
+
+    D, T = q.shape[-1], q.shape[2]
+    return D in (64, 128) or (D == DECODE_WIDE_HEAD_DIM and T > DECODE_MAX_QUERIES and not prefill_wide_off())
+
+
 def _fuse_kv_prefill_reads(trace):
-    """``hip_flash_attn_fwd_ex(q, k, v, mask, False, scale, 0.0, ...)`` whose LSE nobody reads, at head dim 64 / 128,
+    """``hip_flash_attn_fwd_ex(q, k, v, mask, False, scale, 0.0, ...)`` whose LSE nobody reads, at head dim 64 / 128
+    (256 too: ``_prefill_head_dim``),
     with ``mask = kv_position_mask(pos, S)`` (``S`` the keys' length) or ``kv_paged_mask(pos, table, page, num_pages)``
     and ``pos`` int64 ``[B, T]`` -> ``hip_prefill_attn_pos(q, k, v, pos, scale)`` / ``hip_prefill_attn_paged(q, kp, vp,
     pos, table, page, num_pages, scale)``: the kernel takes every row's key count from its position (and every key's
@@ -1530,7 +1539,7 @@ def _fuse_kv_prefill_reads(trace):
         q, k, v, mask = p["q"], p["k"], p["v"], p["mask"]
         if not isinstance(b.output, (tuple, list)) or len(b.output) != 2 or rw.uses(b.output[1]):
             continue
-        if p["causal"] or isinstance(p["dropout_p"], Proxy) or p["dropout_p"] or q.shape[-1] not in (64, 128):
+        if p["causal"] or isinstance(p["dropout_p"], Proxy) or p["dropout_p"] or not _prefill_head_dim(q):
             continue
         if not all(isinstance(t, TensorProxy) for t in (k, v, mask)) or mask.dtype != torch.bool:
             continue

@@ -392,7 +392,9 @@ for _entry, _scale_ptrs in (("lta_decode_attn", 0), ("lta_decode_attn_kv8", 0), 
     register_signature(_entry + "_paged_win", [*_head, c_int, c_float, c_int, c_void_p, c_int, c_int, c_void_p, c_int])
 
 DECODE_MAX_QUERIES = 16
-DECODE_WIDE_HEAD_DIM = 256  # the decode kernels' third head dim (csrc/decode_attention_wide.h); the prefill kernel has none
+# the third head dim of the kernels that read a KV cache: the decode kernels' wide-row variant up to DECODE_MAX_QUERIES
+# rows (csrc/decode_attention_wide.h), the prefill kernel of csrc/prefill_attention_d256.hip past them
+DECODE_WIDE_HEAD_DIM = 256
 
 
 def decode_wide_off() -> bool:
@@ -401,9 +403,18 @@ def decode_wide_off() -> bool:
     return os.environ.get("LTA_DECODE_D256", "1") == "0"
 
 
-def _head_dim_ok(D: int, max_queries) -> bool:
-    """64 / 128 for every kernel that reads a KV cache, 256 as well for the decode kernels (``max_queries`` set)."""
-    return D in (64, 128) or (max_queries is not None and D == DECODE_WIDE_HEAD_DIM)
+def prefill_wide_off() -> bool:
+    """LTA_PREFILL_D256=0 keeps prefills at head dim 256 off the prefill kernel: the compiler leaves them the mask
+    image, the gathers, the dequantisation and the masked forward, as before csrc/prefill_attention_d256.hip (A/B
+    against it).  The wrappers here take 256 either way."""
+    return os.environ.get("LTA_PREFILL_D256", "1") == "0"
+
+
+def _head_dim_ok(D: int, max_queries, rows: int) -> bool:
+    """64 / 128 for every kernel that reads a KV cache.  256 as well: for the decode kernels (``max_queries`` set) at
+    any of their row counts, for the prefill kernels (``max_queries`` None) at more than DECODE_MAX_QUERIES ``rows``
+    only, since the wide-row decode kernel serves every selector and format up to there."""
+    return D in (64, 128) or (D == DECODE_WIDE_HEAD_DIM and (max_queries is not None or rows > DECODE_MAX_QUERIES))
 
 
 def decode_launch_shape(rows: int, S: int):
@@ -489,10 +500,10 @@ def _refusal(fn: str, **operands) -> ValueError:
 
 
 def _cache_operands_ok(q, k, v, cache_dtype, max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
-    """The shape rule of every kernel that checks its operands: 16-bit q [B, Hq, T, D] with D 64 / 128 (the decode
-    kernels: 256 too) and at most ``max_queries`` rows (the decode kernels' DECODE_MAX_QUERIES; None for the prefill
+    """The shape rule of every kernel that checks its operands: 16-bit q [B, Hq, T, D] with D 64 / 128 (256 too: see
+    ``_head_dim_ok``) and at most ``max_queries`` rows (the decode kernels' DECODE_MAX_QUERIES; None for the prefill
     kernel: any number), k / v [B, Hkv, S, D] of ``cache_dtype`` with Hkv dividing Hq."""
-    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and _head_dim_ok(q.shape[-1], max_queries)
+    return (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and _head_dim_ok(q.shape[-1], max_queries, q.shape[2])
             and (max_queries is None or q.shape[2] <= max_queries) and k.dtype == cache_dtype and v.dtype == cache_dtype
             and k.dim() == 4 and k.shape == v.shape and k.shape[-1] == q.shape[-1] and k.shape[0] == q.shape[0]
             and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0)
@@ -608,7 +619,7 @@ def decode_attn_kv8s_pos(q, k8, v8, k_scale, v_scale, pos, scale: float | None =
 # ------------------------------------------------------------------------------------------------
 def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=(),
               max_queries: int | None = DECODE_MAX_QUERIES) -> bool:
-    """16-bit q [B, Hq, T, D] with D 64 / 128 (the decode kernels: 256 too) and at most ``max_queries`` rows (None: any
+    """16-bit q [B, Hq, T, D] with D 64 / 128 (256 too: see ``_head_dim_ok``) and at most ``max_queries`` rows (None: any
     number); pools k / v [Hkv, rows, D] of ``cache_dtype`` read in place (head dim contiguous, 16-byte aligned rows and heads) with Hkv dividing Hq and
     ``rows >= num_pages * page_size``; scale pools uint8 [Hkv, rows, 1]; int64 ``pos`` [B, T] and ``table``
     [B, max_pages >= 1] on q's device; ``page_size`` a power of two >= 16 and ``num_pages`` >= 1, both ints."""
@@ -616,7 +627,7 @@ def _paged_ok(q, k, v, pos, table, page_size, num_pages, cache_dtype, scales=(),
         return False
     if page_size < 16 or page_size & (page_size - 1) or num_pages < 1 or num_pages * page_size >= 2 ** 31:
         return False
-    if not (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and _head_dim_ok(q.shape[-1], max_queries)
+    if not (q.dtype in (torch.bfloat16, torch.float16) and q.dim() == 4 and _head_dim_ok(q.shape[-1], max_queries, q.shape[2])
             and 0 < q.shape[2] and (max_queries is None or q.shape[2] <= max_queries)):
         return False
     unit = 16 // k.element_size()  # elements per 16 bytes
@@ -726,7 +737,8 @@ def _prefill_launch(entry: str, q, k, v, pos, scale: float | None, scales=(), pa
 
 def prefill_attn_pos_supported(q, k, v, pos) -> bool:
     """What the 16-bit prefill kernel takes: bf16 / fp16 q, k, v of one dtype and head dim 64 / 128, GQA head counts,
-    int64 ``pos`` [B, T] with any T >= 1, a cache of at least one key."""
+    int64 ``pos`` [B, T] with any T >= 1, a cache of at least one key.  Head dim 256 (here and in the five predicates
+    below) for T > 16 only: up to 16 rows belong to the decode kernels, which take every selector and format there."""
     return _pos_ok(q, k, pos, None) and _cache_operands_ok(q, k, v, q.dtype, None) and k.shape[2] > 0
 
 
@@ -743,6 +755,11 @@ def prefill_attn_pos(q, k, v, pos, scale: float | None = None, window: int | Non
     int64 [B, T] (need not be monotone).  Row (b, hq, t) attends keys ``0 .. n-1`` with ``n = clamp(pos[b, t] + 1, 0,
     S)``: what ``attn_fwd(q, k, v, causal=False, mask=position_mask(pos, S))[0]`` computes, bit for bit, without the
     mask image and over the key tiles some row can see only.  ``n = 0`` gives a row of zeros, as there.
+
+    At head dim 256 (T > 16; here and on the five wrappers below) the launch is csrc/prefill_attention_d256.hip's
+    kernel: the same rows, keys, dead keys and zeros, but a deferred rescale of O, so the result is held to fp64 and not
+    to the masked forward's bits.  The equalities between formats, between paged and static, and between ``window >=
+    S`` and no window hold there bit for bit too.
 
     ``window`` as ``decode_attn_pos`` takes it: the row attends keys ``max(0, n - window) .. n-1``, what ``attn_fwd``
     computes under ``window_mask(pos, S, window)`` bit for bit, over the key tiles between the workgroup's lowest window

@@ -46,7 +46,8 @@ def _sources():
 # own the AGPR file (without it hipcc swaps them through AGPRs every tile).
 FILE_FLAGS = {"attention_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               "attention_fwd4.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
-              "attention_fwd_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+              "attention_fwd_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+              "prefill_attention_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _compile(src: str, obj: str, is_device: bool, verbose: bool, defines=()) -> str:

@@ -36,6 +36,10 @@
 using namespace lta;
 using namespace lta::attn;
 
+namespace lta {
+int prefill_attn_d256_launch(int dtype, bool e4m3, bool ks, bool paged, bool win, const void* const* a);
+}  // namespace lta
+
 namespace {
 
 constexpr int kBM = 128;  // queries per workgroup
@@ -420,6 +424,8 @@ template <typename KV, bool KS, bool PAGED, bool WIN, typename... A>
 int dispatch(int dtype, int D, A... a) {
   using B16 = __hip_bfloat16;
   constexpr bool kSame = std::is_void_v<KV>;
+  const void* const args[] = {(const void*)&a...};  // D = 256: prefill_attention_d256.hip, its own kernel and launcher
+  if (D == 256) return lta::prefill_attn_d256_launch(dtype, !kSame, KS, PAGED, WIN, args);
   if (dtype == kBF16 && D == 64) return launch<B16, std::conditional_t<kSame, B16, KV>, 64, KS, PAGED, WIN>(a...);
   if (dtype == kBF16 && D == 128) return launch<B16, std::conditional_t<kSame, B16, KV>, 128, KS, PAGED, WIN>(a...);
   if (dtype == kF16 && D == 64) return launch<__half, std::conditional_t<kSame, __half, KV>, 64, KS, PAGED, WIN>(a...);
