@@ -115,6 +115,11 @@ def run(mode: str, args) -> dict:
                 from ..transforms.mxfp4_inference import MXFP4InferenceTransform
 
                 transforms.insert(0, MXFP4InferenceTransform(skip=()))
+            elif mode == "hipgraph_fp8":
+                # e4m3 weights (per-tensor scale, every linear incl. the LM head), bf16 activations
+                from ..transforms.fp8_inference import FP8InferenceTransform
+
+                transforms.insert(0, FP8InferenceTransform(skip=(), activations="bf16"))
             fwd = thunder.jit(model, transforms=transforms)
 
         def once():
@@ -147,7 +152,8 @@ def run(mode: str, args) -> dict:
         "prompt_len": args.prompt_len, "new_tokens": args.new_tokens, "batch_size": args.batch_size,
         "prompt_lengths": args.prompt_lengths, "prefill_chunk": None if mode.startswith("hf_") else args.prefill_chunk,
         "kv_cache_dtype": "model" if mode.startswith("hf_") else args.kv_cache_dtype,
-        "dtype": "mxfp4 weights, bf16 activations" if mode.endswith("mxfp4") else "bf16",
+        "dtype": "mxfp4 weights, bf16 activations" if mode.endswith("mxfp4") else
+                 "e4m3 weights, bf16 activations" if mode.endswith("_fp8") else "bf16",
         "data": "synthetic prompt, random-init weights", "n_gpus": 1,
         "reference_ms": {"thunder+cudagraphs (1xH100)": 542, "eager (1xH100)": 1493},
     }

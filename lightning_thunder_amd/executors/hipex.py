@@ -685,6 +685,54 @@ _MXFP4_LINEAR_IDS = ("custom_op.lta::mxfp4_linear", "custom_op.custom_op_impl_cu
 
 
 # =========================================================================================
+# e4m3 weight-only decode GEMV (lta::fp8_linear_inference with bf16_activations, <= 8 rows): the same set
+# =========================================================================================
+def _fp8_decode_linear_meta(x, q, scale, bias=None, residual=None, act=None, gate_q=None, gate_scale=None, norm=False,
+                            norm_weight=None, eps=1e-5):
+    return TensorProxy(like=x, shape=tuple(x.shape[:-1]) + (q.shape[0],))
+
+
+def _fp8_decode_linear_impl(x, q, scale, bias=None, residual=None, act=None, gate_q=None, gate_scale=None, norm=False,
+                            norm_weight=None, eps=1e-5):
+    from ..ops import fp8_gemv as g8
+
+    x2, r2 = _as_rows(x, residual)
+    kw = dict(bias=bias, residual=r2, act=act, gate_q=gate_q, gate_scale=gate_scale)
+    if g8.gemv_fused_supported(x2, q, scale, norm_weight=norm_weight, **kw):
+        y = g8.gemv_fused(x2, q, scale, norm=norm, norm_weight=norm_weight, eps=eps, **kw)
+    else:  # operands the kernel does not take (alignment, > 8 rows): the same math in torch
+        y = g8.gemv_fused_reference(x2, q, scale, norm=norm, norm_weight=norm_weight, eps=eps, **kw)
+    return _like(x, y)
+
+
+def _fp8_decode_group_impl(x, weights, norm=False, norm_weight=None, eps=1e-5, packed=False):
+    from ..ops import fp8_gemv as g8
+
+    x2, _ = _as_rows(x)
+    if all(g8.gemv_fused_supported(x2, q, s, norm_weight=norm_weight) for q, s in weights):
+        outs = g8.gemv_group(x2, list(weights), norm=norm, norm_weight=norm_weight, eps=eps, packed=packed)
+    else:
+        outs = [g8.gemv_fused_reference(x2, q, s, norm=norm, norm_weight=norm_weight, eps=eps) for q, s in weights]
+        if packed:
+            outs = torch.cat(outs, -1)
+    return _like(x, outs, packed)
+
+
+hip_fp8_decode_linear = ex.register_operator("hip_fp8_decode_linear", meta=_fp8_decode_linear_meta,
+                                             fn=_fp8_decode_linear_impl)
+hip_fp8_decode_linear_group = ex.register_operator("hip_fp8_decode_linear_group", meta=_mxfp4_decode_group_meta,
+                                                   fn=_fp8_decode_group_impl)
+# The norm prologue is recomputed by every wave of the GEMV (whole x rows per wave).  Device-timed A/B on the
+# Llama-2-7B shapes (profiles/fp8_decode_fusion.txt): at 1 row the folded qkv launch ties norm + launch (15.24
+# against 15.28 us) and the folded gated pair loses 3.3 us (25.4 against 22.1: 1376 workgroups each repeat the
+# row statistics); from 2 rows on the folded launch loses at both sites (qkv 23.0 against 16.9 us, and 3x at 8
+# rows).  So never more than 1 row; the gated site at 1 row is the known loss of this value.
+_FP8_NORM_MAX_ROWS = 1
+_FP8_LINEAR_IDS = ("custom_op.lta::fp8_linear_inference",
+                   "custom_op.custom_op_impl_custom_op_lta_fp8_linear_inference")
+
+
+# =========================================================================================
 # Decode fusion: one rewrite for both weight kinds, over operand records of the candidate projections
 # =========================================================================================
 def _decode_record(b, x, w, bias=None, residual=None, act=None, gate=None, norm=False, norm_weight=None, eps=1e-5):
@@ -719,6 +767,20 @@ def _mxfp4_decode_candidate(b):
     return _decode_record(b, x, (p["q"], p["s"]), bias)
 
 
+def _fp8_decode_candidate(b):
+    if b.sym.id not in _FP8_LINEAR_IDS:
+        return None
+    p = operands(b, ("x", "q", "scale", "bias", "bf16_activations"))
+    x, bias = p["x"], p["bias"]
+    if p["bf16_activations"] is not True:
+        return None  # the W8A8 program is left as it is
+    if not isinstance(x, TensorProxy) or x.device.type != "cuda" or x.dtype != torch.bfloat16:
+        return None
+    if any(getattr(v, "requires_grad", False) for v in (x, bias, b.output)):
+        return None  # the op's autograd stays with the custom op
+    return _decode_record(b, x, (p["q"], p["scale"]), bias)
+
+
 class _DecodeKind(NamedTuple):
     """What the decode fusion needs to know about a weight format."""
     candidate: Callable  # bound symbol -> operand record, or None
@@ -736,6 +798,9 @@ _BF16_DECODE = _DecodeKind(_bf16_decode_candidate, hip_decode_linear, hip_decode
 _MXFP4_DECODE = _DecodeKind(_mxfp4_decode_candidate, hip_mxfp4_decode_linear, hip_mxfp4_decode_linear_group,
                             _MXFP4_NORM_MAX_ROWS, lower=True, mul=("mul", "torch_mul"), silu=("silu", "torch_silu"),
                             switch="LTA_MXFP4_DECODE_FUSION")
+_FP8_DECODE = _DecodeKind(_fp8_decode_candidate, hip_fp8_decode_linear, hip_fp8_decode_linear_group,
+                          _FP8_NORM_MAX_ROWS, lower=True, mul=("mul", "torch_mul"), silu=("silu", "torch_silu"),
+                          switch="LTA_FP8_DECODE_FUSION")
 
 
 def _silu_arg(b, names):
@@ -2001,6 +2066,9 @@ _PASSES = (
             message="hipex: decode GEMV fusion ({gate} gated pair(s), {norm} norm prologue(s))"),
     partial(_fuse_decode, kind=_MXFP4_DECODE, folds=("gate", "act", "residual", "norm", "group"),
             message="hipex: MXFP4 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
+                    "{norm} norm prologue(s), {group} group(s))"),
+    partial(_fuse_decode, kind=_FP8_DECODE, folds=("gate", "act", "residual", "norm", "group"),
+            message="hipex: e4m3 decode GEMV fusion ({gate} gated pair(s), {act} activation(s), {residual} residual(s), "
                     "{norm} norm prologue(s), {group} group(s))"),
     _fuse_swiglu_gemms, _fuse_kv_cache_writes, _fuse_kv_position_reads, _fuse_kv8_reads, _fuse_kv_paged_reads,
     _fuse_kv_prefill_reads,

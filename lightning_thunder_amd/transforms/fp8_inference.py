@@ -3,14 +3,22 @@
 ``te_groupedmm_fp8``).
 
 Weights are quantized once, in ``transform_module``, to OCP e4m3 with a per-tensor scale
-(``q = fp8(w * 448 / amax(w))``).  At run time each call quantizes the activation with current
-per-tensor scaling (one amax pass + one cast pass, ``ops/fp8.py``) and multiplies on the CDNA4
-block-scaled MFMA fp8 GEMM (``csrc/gemm.hip`` ``gemm_nt_fp8_kernel``, the dequantisation
-``1/(sx*sw)`` folded into the epilogue).  Rows are padded to the GEMM's 256-row tile so decode
-(M = batch) runs on the same kernel; the weight is read from HBM in fp8, i.e. half the bytes of a
-bf16 GEMV.  Grouped (MoE) experts (``GroupedLinear``, weight [G, N, K]) are quantized per expert
+(``q = fp8(w * 448 / amax(w))``).  ``activations`` chooses what multiplies them at run time:
+
+* ``"fp8"`` (default, W8A8): each call quantizes the activation with current per-tensor scaling (one amax
+  pass + one cast pass, ``ops/fp8.py``) and multiplies on the CDNA4 block-scaled MFMA fp8 GEMM
+  (``csrc/gemm.hip`` ``gemm_nt_fp8_kernel``, the dequantisation ``1/(sx*sw)`` folded into the epilogue).
+  Rows are padded to the GEMM's 256-row tile, so decode (M = batch) runs on the same kernel.
+* ``"bf16"`` (weight-only, W8A16): bf16 activations are left as they are.  Up to 32 rows (decode, short
+  prompts) run the e4m3 weight-streaming GEMV (``csrc/gemv_fp8.hip``, ``ops/fp8_gemv.py``) in chunks of 8
+  rows: one launch, half the weight bytes of a bf16 GEMV, no activation quantisation; in a compiled
+  program with up to 8 rows the HIP executor rewrites the op into ``hip_fp8_decode_linear`` with the
+  surrounding norm / SwiGLU / residual folded into the launch and q / k / v grouped
+  (``executors/hipex.py`` ``_fuse_decode``).  More rows dequantise the weight to bf16 and run the bf16 GEMM.
+
+Grouped (MoE) experts (``GroupedLinear``, weight [G, N, K]) are quantized per expert
 (one scale per expert) and run on the grouped fp8 MFMA kernel ``lta_gemm_grouped_nt_fp8``
-(``lta::fp8_grouped_mm_inference``, the ``te_groupedmm_fp8`` counterpart): each workgroup finds
+(``lta::fp8_grouped_mm_inference``, the ``te_groupedmm_fp8`` counterpart) in both modes: each workgroup finds
 its (expert, row tile) from the device offsets, so routing needs no host synchronisation.
 
 The quantized linear is a ``torch.library`` custom op (``lta::fp8_linear_inference``), so it is
@@ -38,16 +46,30 @@ def dequantize_e4m3(q: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) 
     return (q.view(torch.float8_e4m3fn).float() / scale).to(dtype)
 
 
+GEMV_ROWS = 32  # rows up to which the weight-only path runs the GEMV (as transforms/mxfp4_inference.py)
+
+
 def _gpu_path(x2: torch.Tensor, K: int, N: int) -> bool:
     return x2.is_cuda and x2.dtype == torch.bfloat16 and K % 256 == 0 and N % 256 == 0
 
 
 @torch.library.custom_op("lta::fp8_linear_inference", mutates_args=())
 def fp8_linear_inference(x: torch.Tensor, qweight: torch.Tensor, w_scale: torch.Tensor,
-                         bias: torch.Tensor | None = None) -> torch.Tensor:
+                         bias: torch.Tensor | None = None, bf16_activations: bool = False) -> torch.Tensor:
     N, K = qweight.shape
     x2 = x.reshape(-1, K)
-    if _gpu_path(x2, K, N):
+    if bf16_activations and x2.is_cuda and x2.dtype == torch.bfloat16 and K % 16 == 0:
+        from ..ops import fp8_gemv as g8
+
+        M = x2.shape[0]
+        if M <= GEMV_ROWS:  # decode and short prompts: 8 rows per pass over the e4m3 weight
+            y = torch.cat([g8.gemv(x2[i:i + g8.GEMV_MAX_ROWS], qweight, w_scale, bias)
+                           for i in range(0, M, g8.GEMV_MAX_ROWS)]) if M > g8.GEMV_MAX_ROWS else \
+                g8.gemv(x2, qweight, w_scale, bias)
+        else:
+            y = torch.nn.functional.linear(x2, dequantize_e4m3(qweight, w_scale, x.dtype),
+                                           None if bias is None else bias.to(x.dtype))
+    elif not bf16_activations and _gpu_path(x2, K, N):
         from ..ops import fp8 as f8
 
         M = x2.shape[0]
@@ -66,12 +88,12 @@ def fp8_linear_inference(x: torch.Tensor, qweight: torch.Tensor, w_scale: torch.
 
 
 @fp8_linear_inference.register_fake
-def _fp8_linear_inference_fake(x, qweight, w_scale, bias=None):
+def _fp8_linear_inference_fake(x, qweight, w_scale, bias=None, bf16_activations=False):
     return x.new_empty((*x.shape[:-1], qweight.shape[0]))
 
 
 def _setup(ctx, inputs, output):
-    x, qweight, w_scale, bias = inputs
+    x, qweight, w_scale, bias, _ = inputs
     ctx.save_for_backward(qweight, w_scale)
     ctx.xdtype = x.dtype
     ctx.has_bias = bias is not None
@@ -81,7 +103,7 @@ def _backward(ctx, g):
     qweight, w_scale = ctx.saved_tensors
     gx = g @ dequantize_e4m3(qweight, w_scale, g.dtype)
     gb = g.reshape(-1, g.shape[-1]).sum(0) if ctx.has_bias else None
-    return gx, None, None, gb
+    return gx, None, None, gb, None
 
 
 fp8_linear_inference.register_autograd(_backward, setup_context=_setup)
@@ -151,18 +173,26 @@ class _FP8GroupedForward:
 
 
 class _FP8Forward:
-    def __init__(self, mod):
+    def __init__(self, mod, bf16_activations: bool = False):
         self.mod = mod
+        self.bf16_activations = bf16_activations
 
     def __call__(self, x):
         m = self.mod
+        if self.bf16_activations:
+            return fp8_linear_inference(x, m.fp8_weight, m.fp8_scale, m.bias, True)
         return fp8_linear_inference(x, m.fp8_weight, m.fp8_scale, m.bias)
 
 
 class FP8InferenceTransform(Transform):
-    """Quantizes ``nn.Linear`` weights (all, or those named in ``modules``) to e4m3 for inference."""
+    """Quantizes ``nn.Linear`` weights (all, or those named in ``modules``) to e4m3 for inference.
+    ``activations``: ``"fp8"`` (W8A8, per-call activation quantisation) or ``"bf16"`` (weight-only)."""
 
-    def __init__(self, modules: list[str] | None = None, skip: tuple[str, ...] = ("lm_head",)):
+    def __init__(self, modules: list[str] | None = None, skip: tuple[str, ...] = ("lm_head",),
+                 activations: str = "fp8"):
+        if activations not in ("fp8", "bf16"):
+            raise ValueError(f"activations must be 'fp8' or 'bf16', got {activations!r}")
+        self.bf16_activations = activations == "bf16"
         self.modules = modules
         self.skip = skip
         self.quantized: list[str] = []
@@ -193,7 +223,7 @@ class FP8InferenceTransform(Transform):
             del m.weight
             m.register_buffer("fp8_weight", q.to(dev))
             m.register_buffer("fp8_scale", s.to(dev))
-            m.forward = _FP8Forward(m)
+            m.forward = _FP8Forward(m, self.bf16_activations)
             self.quantized.append(name)
 
     def transform_state_dict_for_submodule(self, model, submodule_name, state_dict):
